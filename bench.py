@@ -3,12 +3,20 @@
 ViT-Base masked modeling with the difference-map decoder, 224x224 5-bin voxels, bf16, batch 64 per MI355X).
 
   python bench.py --gpus N --steps K --warmup W        (N>1: launched by torch.distributed.run, one rank per GPU)
+  python bench.py ... --dump-outputs DIR               (also writes what the last timed step computed as DIR/*.npy)
+  python bench.py ... --full                           (also every secondary figure listed below)
 
 One "step" = mask-noise draw -> forward -> backward -> (N>1: bucketed RCCL gradient all-reduce, overlapped with
-backward) -> fused AdamW -> zero_grad, on a synthetic batch that is already resident in HBM (voxel grids made by the
-K1 kernel from synthetic event clips before the timed region). Prints ONE JSON line on rank 0.
+backward) -> fused AdamW -> zero_grad, on a synthetic batch that is already resident in HBM (voxel grids of synthetic
+event clips, made before the timed region). Prints ONE JSON line on rank 0.
 
-Extra objects on the same line:
+A plain run sets up, warms up, times K steps, writes its outputs when --dump-outputs is given and prints the line:
+metric / value (samples/s, the mean over exactly K steps) / unit / higher_is_better / dtype / ms_per_step, with the
+configuration, the final loss and the launch mode beside them. Everything that takes runs of its own is behind --full.
+
+Extra objects on the same line with --full:
+  ms_per_step_median / ms_per_step_min   HIP events around single steps after the timed region (min(K, 50) more steps).
+  dp_tail_ms_per_rank   N>1: per-rank tail of the data-parallel step (10 more steps).
   roofline      dominant kernel = the forward / data-gradient bf16 MFMA GEMM family; achieved = algorithmic FLOPs of its launches in
                 one step / the sum of their durations INSIDE the replayed step (in-kernel wall-clock stamps, StampedStep);
                 `frac_warm` = the same launches re-launched back to back between HIP events; peak = 2.5 PFLOP/s dense bf16
@@ -17,6 +25,8 @@ Extra objects on the same line:
                 against the 8 TB/s HBM peak, HIP-event timed.
   cpu_baseline  the CPU oracle (oracle/model_oracle.py: torch fp32 restatement, kind "port") timed on this box's host
                 cores on a bounded sample of the same workload (rank 0, N=1 only).
+  loader_chain / end_to_end   the loader's whole chain on the GPU, and chain + step back to back.
+--no-kernel-timing and --no-cpu-baseline drop parts of the --full set.
 """
 import argparse
 import json
@@ -89,9 +99,12 @@ def build(args, device):
 
 
 def make_batch(args, device, rank):
-    """Synthetic clips -> voxel grids through the K1 kernel; difference-map targets ~ N(0,1)."""
-    from eventpretrain_amd.dataset.dataset_utils.events_to_voxel_grid import voxel_grid_batch
+    """Synthetic clips -> voxel grids; difference-map targets ~ N(0,1). The grids the step reads are the CPU
+    oracle's histogram of the clips (oracle/voxel_oracle.c, bit-identical to the reference's events_to_voxel_grid): the K1
+    kernel sums with float atomics whose order, and so the last bits, may change from run to run, and the step's inputs
+    must be the same in every run and every build (--dump-outputs). The clips stay resident in HBM for K1's own figure."""
     from eventpretrain_amd.testing import synthetic_events
+    from oracle.voxel_oracle import voxel_grid_batch as oracle_voxel_grid_batch
     S = 64 if args.model == "tiny" else 224
     n_ev = 10_000 if args.model == "tiny" else 100_000
     B = args.batch
@@ -105,9 +118,11 @@ def make_batch(args, device, rank):
         if i % 2:
             e[:, 3] = 1.0 - e[:, 3]
         evs.append(e)
-    ev = torch.from_numpy(np.concatenate(evs, 0)).to(device)
-    off = torch.arange(0, (B + 1) * n_ev, n_ev, dtype=torch.int64, device=device)
-    vox = voxel_grid_batch(ev, off, 5, (S, S))
+    ev_host = np.concatenate(evs, 0)
+    off_host = np.arange(0, (B + 1) * n_ev, n_ev, dtype=np.int64)
+    ev = torch.from_numpy(ev_host).to(device)
+    off = torch.from_numpy(off_host).to(device)
+    vox = torch.from_numpy(oracle_voxel_grid_batch(ev_host, off_host, 5, (S, S))).to(device)
     g = torch.Generator(device="cpu").manual_seed(1 + rank)
     if CONFIGS[args.config][5] == "clip":
         tgt = torch.randn(B, 197, 512, generator=g).to(device)      # frozen-CLIP image tokens: an input tensor
@@ -372,6 +387,33 @@ def cpu_voxel_baseline():
                 sample="oracle/voxel_oracle.c, %d x (8 clips x 100k events), %.2f s" % (reps, dt_))
 
 
+DUMP_SAMPLE = 4096         # elements of each parameter tensor written by --dump-outputs (all of it when smaller)
+
+
+def dump_outputs(path, loss, model):
+    """What the timed path hands its caller after its last step, as .npy files under `path`: the loss (float64 [1]) and the
+    weights the step updated -- `weights_sample` (float32, the elements at fixed seeded positions of every parameter, in
+    named_parameters() order) and `weights_checksums` (float64 [n_params, 3]: sum, sum of |x|, sum of x^2 of each whole
+    tensor). A few MB in all."""
+    os.makedirs(path, exist_ok=True)
+    rng = np.random.default_rng(20240917)
+    samples, sums = [], []
+    with torch.no_grad():
+        for _name, p in model.named_parameters():
+            flat = p.detach().reshape(-1)
+            n = flat.numel()
+            if n > DUMP_SAMPLE:
+                idx = torch.from_numpy(np.sort(rng.integers(0, n, DUMP_SAMPLE))).to(flat.device)
+                samples.append(flat.index_select(0, idx).float())
+            else:
+                samples.append(flat.float())
+            d = flat.double()
+            sums.append(torch.stack([d.sum(), d.abs().sum(), (d * d).sum()]))
+    np.save(os.path.join(path, "loss.npy"), np.array([float(loss.item())], dtype=np.float64))
+    np.save(os.path.join(path, "weights_sample.npy"), torch.cat(samples).cpu().numpy().astype(np.float32))
+    np.save(os.path.join(path, "weights_checksums.npy"), torch.stack(sums).cpu().numpy().astype(np.float64))
+
+
 def self_launch(n, argv):
     """`python bench.py --gpus N` (N > 1) outside torch.distributed.run: start
         python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port <free> bench.py <same args>
@@ -406,8 +448,13 @@ def main():
     ap.add_argument("--batch", type=int, default=64, help="per-GPU batch")
     ap.add_argument("--model", default="base", choices=["base", "small", "tiny"])
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "fp32"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-kernel-timing", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure every secondary figure (median step time, kernel timing and roofline, K1, loader chain, "
+                         "CPU baselines, data-parallel tail); a plain run only times the steps")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's loss and a fixed sample of the updated weights as DIR/*.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
+    ap.add_argument("--no-kernel-timing", action="store_true", help="with --full: skip kernel timing, K1 and the loader chain")
     ap.add_argument("--bucket-mb", type=float, default=64.0)
     ap.add_argument("--no-graph", action="store_true", help="launch every kernel from Python each step (no HIP graph)")
     ap.add_argument("--wgrad-chunks", type=int, default=4,
@@ -419,6 +466,8 @@ def main():
     ap.add_argument("--dist-backend", default="nccl", choices=["nccl", "gloo"],
                     help="nccl = RCCL over xGMI (the product path); gloo = rehearsal of the N > 1 control flow with several ranks on ONE card")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     # ---- N > 1 from a plain `python bench.py --gpus N`: start the ranks as a CHILD process group (one rank per GPU over RCCL) and
     # relay. This runs before anything touches the GPU runtime: no HIP call, no torch.cuda.is_available(), no library load
@@ -510,6 +559,8 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
     final_loss = float(loss.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, loss, model)
 
     ms = elapsed / args.steps * 1e3
     value = args.batch * world * args.steps / elapsed
@@ -533,21 +584,23 @@ def main():
         result["step_tflops_per_gpu"] = fl_sample * args.batch / (ms * 1e-3) / 1e12
         result["step_mfma_frac"] = result["step_tflops_per_gpu"] / MFMA_BF16_PEAK_TFLOPS
 
-    # ---- median of per-step times (HIP events around single steps, after the timed region; SURVEY.md 8d asks for the
-    # median; `value` above stays the mean over exactly K steps as the driver's contract says)
-    n_med = min(args.steps, 50)
-    evs = [torch.cuda.Event(enable_timing=True) for _ in range(n_med + 1)]
-    barrier()
-    evs[0].record()
-    for i in range(n_med):
-        step()
-        evs[i + 1].record()
-    barrier()
-    per = sorted(evs[i].elapsed_time(evs[i + 1]) for i in range(n_med))
-    result["ms_per_step_median"] = per[n_med // 2]
-    result["ms_per_step_min"] = per[0]
+    # ---- --full only from here on: what takes steps or runs of its own beyond the timed region
+    if args.full:
+        # median of per-step times (HIP events around single steps, after the timed region; SURVEY.md 8d asks for the
+        # median; `value` above stays the mean over exactly K steps as the driver's contract says)
+        n_med = min(args.steps, 50)
+        evs = [torch.cuda.Event(enable_timing=True) for _ in range(n_med + 1)]
+        barrier()
+        evs[0].record()
+        for i in range(n_med):
+            step()
+            evs[i + 1].record()
+        barrier()
+        per = sorted(evs[i].elapsed_time(evs[i + 1]) for i in range(n_med))
+        result["ms_per_step_median"] = per[n_med // 2]
+        result["ms_per_step_min"] = per[0]
 
-    if multi and getattr(executor, "plan", None) is not None:
+    if args.full and multi and getattr(executor, "plan", None) is not None:
         # per-rank tail of the data-parallel step: from "last weight-gradient chunk computed" to "every all-reduce and update
         # part done" on the step's stream -- what is NOT hidden behind compute (diagnoses the 1 -> 8 scaling from one run)
         executor.plan.timing = []
@@ -561,7 +614,7 @@ def main():
         dist.all_gather(gathered, t_)
         result["dp_tail_ms_per_rank"] = [round(float(g_.item()), 4) for g_ in gathered]
 
-    if rank == 0 and not args.no_kernel_timing:
+    if args.full and rank == 0 and not args.no_kernel_timing:
         # ---- dominant kernel, HIP events around every GEMM launch of real steps (instrumented, after the timed region)
         from eventpretrain_amd import ops as _ops
         timer = GemmTimer()
@@ -799,7 +852,7 @@ def main():
     if multi:
         dist.barrier()
 
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and headline and args.model == "base":
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and headline and args.model == "base":
         n_thr = os.cpu_count() or 1
         try:
             result["cpu_baseline"] = cpu_baseline(fcfg, n_thr, 16, 6)          # all host cores
