@@ -269,16 +269,28 @@ __device__ void draw_distinct(uint64_t *keys, int *a, int *b, int *scratch, int 
   }
   __syncthreads();
   if (distinct < k && tid == 0) {
-    // fewer distinct candidates than asked for (needs more repeats than the slack holds: practically never): top up with the smallest
-    // rows not drawn yet, so that exactly k rows leave -- the offsets of every later table depend on it
-    int have = distinct;
+    // fewer distinct candidates than asked for (needs more repeats than the slack holds: rare, small windows only): top up with the
+    // smallest rows not drawn yet, so that exactly k rows leave -- the offsets of every later table depend on it. Every distinct
+    // candidate is selected here, so the sorted list is rewritten as the merge of the candidates (keys, ascending) with the top-up rows
+    // (the merge kernel and the fused K1 need it ascending); the draw-order list keeps its draws and appends the top-up.
+    int have = SORTED_OUT ? 0 : distinct, extra = k - distinct;
     int64_t v = 0;
     int i = 0;
-    while (have < k && v < n) {
+    while (have < k) {
       while (i < np2 && (int64_t)(keys[i] >> 16) < v) ++i;
-      if (i < np2 && (int64_t)(keys[i] >> 16) == v) { ++v; continue; }
-      out[have++] = v++;                                       // (sorted output loses its order here; the merge only needs a set for
-    }                                                          //  n this small -- and the caller's slack makes this path unreachable)
+      const int64_t cv = i < np2 ? (int64_t)(keys[i] >> 16) : n;          // next candidate value >= v (n: none left)
+      if (cv == v && i < np2) {
+        if (SORTED_OUT) out[have++] = v;
+        ++v;
+      } else if (extra > 0 && v < n) {
+        out[have++] = v++;
+        --extra;
+      } else if (SORTED_OUT && i < np2) {
+        v = cv;                                                            // no top-up row left to place: jump to the next candidate
+      } else {
+        break;                                                             // (k > n: nothing more to give)
+      }
+    }
   }
   __syncthreads();
 }

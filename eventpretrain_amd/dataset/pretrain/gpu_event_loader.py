@@ -8,15 +8,19 @@ the clip files.
     loader  = GpuEventLoader(args, samples, batch_size=64, n_batches=len(dataset) // 64, seed=args.seed, first_sample=rank * 64)
     pr_rec_one_epoch(args, model, loader, optimizer, epoch, loss_scaler)          # yields the dict batches the trainers take
 
-Per batch: the clips are packed into a pinned slot on a worker thread (one batch ahead), uploaded on a copy stream while the previous
-training step runs, and turned into (events_voxel_grid [B,bins,S,S], sub_frame [B,C,S,S]) by one graph replay. The decisions come
-from the counter stream keyed by (seed, step, first_sample + i): reproducible per sample, independent of worker scheduling."""
+Per batch: each clip's window is picked on the host and only its rows are packed into a pinned slot on a worker thread (one batch
+ahead), uploaded on a copy stream while the previous training step runs, and turned into (events_voxel_grid [B,bins,S,S],
+sub_frame [B,C,S,S]) by one graph replay. The decisions come from the counter stream keyed by (seed, step, first_sample + i):
+reproducible per sample, independent of worker scheduling. The window start is the plan kernel's own rule (word 0 of the stream,
+s0 = (w0 * (n - fix)) >> 32, uniform over the WHOLE clip as get_random_index draws it); the plan then sees a clip of fix rows, which it
+takes whole, and draws the same counts and crop boxes it would have drawn for the uncut clip."""
 from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 import torch
 
 from ... import _lib
+from ..augmentation.events_augment import philox_words
 from .gpu_input_pipeline import GpuInputPipeline
 
 
@@ -27,15 +31,18 @@ class GpuEventLoader:
                  frame_key="sub_frame", step0=0):
         """`samples`: a re-iterable (one pass per epoch) of (events, frame, name); `n_batches`: batches per epoch (a short last batch is
         dropped, as the reference's training loader does: drop_last=True). `max_events_per_clip`: capacity per clip of the device
-        buffer (longer clips are cut to their FIRST rows before the window pick; default 2 x fix_events_num). `frame_shape` = (C,Hf,Wf)
+        buffer, at least (and by default) fix_events_num -- only the picked window of a clip is uploaded. `frame_shape` = (C,Hf,Wf)
         when the samples carry frame targets. `step0`: the counter stream's step of the first batch (continues across epochs)."""
         _lib.require_device()
         self.args, self.samples, self.B, self.n_batches = args, samples, int(batch_size), int(n_batches)
         self.dev = torch.device(args.device)
-        self.cap = int(max_events_per_clip or 2 * int(args.fix_events_num))
+        self.fix = int(args.fix_events_num)
+        self.cap = int(max_events_per_clip or self.fix)
+        if self.cap < self.fix:
+            raise ValueError(f"GpuEventLoader: max_events_per_clip ({self.cap}) must hold a window of fix_events_num ({self.fix}) rows")
         self.frame_key, self.frame_shape = frame_key, None if frame_shape is None else tuple(int(v) for v in frame_shape)
         self.pipe = GpuInputPipeline(args, seed=seed)
-        self.first_sample, self.step = int(first_sample), int(step0)
+        self.seed, self.first_sample, self.step = int(seed), int(first_sample), int(step0)
         B, cap = self.B, self.cap
         self.ev = torch.zeros(B * cap, 4, dtype=torch.float64, device=self.dev)
         self.frames = None if self.frame_shape is None else torch.zeros(B, *self.frame_shape, dtype=torch.float32, device=self.dev)
@@ -52,11 +59,14 @@ class GpuEventLoader:
     def __len__(self):
         return self.n_batches
 
-    def _pack(self, it, slot):
-        """Host half of one batch (worker thread): B samples -> the pinned slot. -> (rows, names) or None at the end of the pass."""
+    def _pack(self, it, slot, step):
+        """Host half of one batch (worker thread): B samples -> their windows in the pinned slot. `step`: the counter stream's step of
+        THIS batch (the pack runs one batch ahead). -> (rows, names) or None at the end of the pass."""
         if self._slot_free[slot] is not None:
             self._slot_free[slot].synchronize()
         ev_h, off_h, fr_h = self._pin_ev[slot].numpy(), self._pin_off[slot].numpy(), self._pin_fr[slot]
+        fix = self.fix
+        w0 = philox_words(self.seed, step, self.first_sample + np.arange(self.B), 0, 1)[:, 0]      # evp_events_plan_batch's window word
         names, n = [], 0
         off_h[0] = 0
         for i in range(self.B):
@@ -67,8 +77,9 @@ class GpuEventLoader:
             e = np.asarray(events, dtype=np.float64)
             if e.ndim != 2 or e.shape[1] != 4:
                 raise ValueError("GpuEventLoader: events must be float64 [n,4] (x,y,t,p)")
-            k = min(e.shape[0], self.cap)
-            ev_h[n:n + k] = e[:k]
+            s0 = (int(w0[i]) * (e.shape[0] - fix)) >> 32 if e.shape[0] > fix else 0
+            k = min(e.shape[0], fix)
+            ev_h[n:n + k] = e[s0:s0 + k]
             n += k
             off_h[i + 1] = n
             if fr_h is not None:
@@ -96,7 +107,7 @@ class GpuEventLoader:
     def __iter__(self):
         it = iter(self.samples)
         self.chain.set_state(self.step, self.first_sample)
-        fut = self._pool.submit(self._pack, it, 0)
+        fut = self._pool.submit(self._pack, it, 0, self.step)
         for b in range(self.n_batches):
             slot = b & 1
             packed = fut.result()
@@ -105,7 +116,7 @@ class GpuEventLoader:
             n, names = packed
             up = self._upload(slot, n)
             if b + 1 < self.n_batches:
-                fut = self._pool.submit(self._pack, it, slot ^ 1)      # the next batch is packed while this one is uploaded and trained on
+                fut = self._pool.submit(self._pack, it, slot ^ 1, self.step + 1)      # the next batch is packed while this one is uploaded and trained on
             cur = torch.cuda.current_stream(self.dev)
             cur.wait_event(up)
             vox, tgt = self.chain.run_next()

@@ -101,7 +101,8 @@ int evp_events_build_added_f64(const double *events, const int64_t *win_begin, i
  * normal noise columns of the copies): clip c (rows [win_begin[c], win_end[c]) of some event array, n_c of them) gets
  * erase_offsets[c+1] - erase_offsets[c] DISTINCT rows in erase_idx (ascending, clip-relative) and add_offsets[c+1] - add_offsets[c]
  * distinct rows in add_idx (draw order) with add_noise [.,3] ~ N(0,1.5), N(0,1.5), N(0,0.001) -- uniform draws without replacement
- * from Philox4x32-10 keyed by (seed, step, first_sample + c). The COUNTS (the offsets) are the caller's: two numbers per clip, uniform
+ * from Philox4x32-10 keyed by (seed, step, first_sample + c); when a count is close to n_c and the drawn candidates hold fewer distinct
+ * rows, the list is topped up with the smallest rows not drawn (the erase list stays ascending). The COUNTS (the offsets) are the caller's: two numbers per clip, uniform
  * in [int(0.001 n), int(0.01 n)). max_per_clip = the largest count of any list (<= ~7200; an upper bound will do). step_first_dev
  * (optional, device int64[2]) overrides (step, first_sample) at run time, so that one captured HIP graph serves every batch. Feeds
  * evp_events_erase_add(_win)_f64. */
@@ -127,7 +128,8 @@ int evp_events_sorted_check(const double *events, const int64_t *clip_offsets, i
  * events_to_voxel_grid): the voxel grids of the clips [win_begin[c], win_end[c]) of `events` MINUS the rows erase_idx (window-relative,
  * ascending, erase_offsets [n_clips+1]) PLUS added_rows (float64 [.,4] x,y,t,p, time-sorted per clip as evp_events_erase_add_*'s workspace
  * holds them, add_offsets [n_clips+1]) -- without writing the merged clip: the grid is a sum over the kept rows, the order only decides
- * t0 / t1 (min / max stamp of the merged clip). max_window >= every window's rows (<= 393216: one bit per row in LDS). Window stamps
+ * t0 / t1 (min / max stamp of the merged clip). max_window (<= 393216) sizes the erased-row bitmap in LDS, one bit per row: it should be
+ * >= every window's rows; rows of a longer window are looked up in the erase list by binary search (same grid, slower). Window stamps
  * non-decreasing is verified on the device; a clip that fails is redone by a full scan. workspace: n_clips * (bins + 5) int64.
  * view_params (optional, device int32 [n_clips,6] as evp_view_augment_f32 takes them): the grids leave THROUGH the view augmentation --
  * out is then float32 [n_clips, bins, view_h, view_w] = evp_view_augment_f32 of the grids, which are never stored; NULL: out holds the

@@ -113,3 +113,26 @@ def assert_ids_equal_up_to_ties(noise, keep, ref, got, what=""):
         if not (cnt > 1).any():
             for k in range(3):
                 assert np.array_equal(ref[k][b], got[k][b]), (what, b, k)
+
+
+# ----------------------------------------------------------------------------------------------- distribution checks
+def normal_cdf(x):
+    """Standard normal CDF, elementwise over a numpy array."""
+    from math import erfc, sqrt
+    x = np.asarray(x, dtype=np.float64)
+    return 0.5 * np.vectorize(erfc)(-x / sqrt(2.0))
+
+
+def chi2_isf(p, dof):
+    """Upper p-quantile of the chi-square distribution with `dof` degrees of freedom (Wilson-Hilferty; the normal quantile by
+    bisection). Within a few per cent of the exact value for dof >= 3 and p >= 1e-9: enough for a p ~ 1e-6 test threshold."""
+    from math import erfc, sqrt
+    lo, hi = 0.0, 40.0
+    for _ in range(200):
+        mid = 0.5 * (lo + hi)
+        if 0.5 * erfc(mid / sqrt(2.0)) > p:
+            lo = mid
+        else:
+            hi = mid
+    z, k = 0.5 * (lo + hi), float(dof)
+    return k * (1.0 - 2.0 / (9.0 * k) + z * sqrt(2.0 / (9.0 * k))) ** 3

@@ -823,7 +823,7 @@ def test_gpu_event_loader_is_a_drop_in_for_the_epoch_loop():
     g = torch.Generator().manual_seed(3)
     samples = [(synthetic_events(400 + i, n, width=640, height=480), torch.randn(1, 480, 640, generator=g), f"clip{i}") for i, n in enumerate(sizes)]
     loader = GpuEventLoader(a, samples, batch_size=B, n_batches=3, seed=21, first_sample=8, frame_shape=(1, 480, 640), step0=5,
-                            max_events_per_clip=40_000)          # (the default capacity, 2 x fix_events_num, would cut the 40 k clip)
+                            max_events_per_clip=40_000)          # (a capacity above fix_events_num: only the picked windows are uploaded)
     got = [(b["events_voxel_grid"].clone(), b["sub_frame"].clone(), list(b["image_name"])) for b in loader]
     assert len(got) == 2 and got[1][2] == ["clip4", "clip5", "clip6", "clip7"] and loader.step == 7
     pipe = GpuInputPipeline(a, seed=21)
