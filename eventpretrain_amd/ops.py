@@ -553,11 +553,13 @@ class _DeferredGrads:
                         if ns > 1:
                             kper = ((rows // 64 + ns - 1) // ns) * 64
                             ns = (rows + kper - 1) // kper
+                            if T_ == 256 and rows - (ns - 1) * kper < 96:
+                                ns -= 1              # a G4 slice needs K >= 96: the short tail joins the slice before it
                             numel = n_out * k_in
                             ws = torch.empty(ns * numel, dtype=torch.float32, device=dev)
                             for sidx in range(ns):
                                 k0 = sidx * kper
-                                kk = min(kper, rows - k0)
+                                kk = rows - k0 if sidx == ns - 1 else kper
                                 rows_.append((dy.data_ptr() + k0 * n_out * 2, x.data_ptr() + k0 * k_in * 2, ws.data_ptr() + sidx * numel * 4,
                                               n_out, k_in, kk, n_out, k_in, k_in, 0, 0, 0, tm, tn))
                             post.append((ws, gt, ns, numel, acc))
@@ -570,6 +572,9 @@ class _DeferredGrads:
                             cs_ptr = bt.data_ptr()
                         rows_.append((dy.data_ptr(), x.data_ptr(), gt.data_ptr(), n_out, k_in, rows, n_out, k_in, k_in, acc, cs_acc, cs_ptr, tm, tn))
                     rows_.sort(key=lambda r_: -r_[5])           # longest K first
+                    if T_ == 256:
+                        for r_ in rows_:
+                            _check_g4_problem(r_[3], r_[4], r_[5])
                     probs = np.zeros(len(rows_), dtype=pdt)
                     weights = []
                     for i, r_ in enumerate(rows_):
@@ -619,6 +624,14 @@ class _DeferredGrads:
             else:
                 steps.append(st)
         return steps
+
+
+def _check_g4_problem(M, N, K):
+    """The G4 grouped body's contract (include/evtpretrain.h): its tables live on the device, where nothing checks them,
+    and its prologue consumes three 32-row stages with unbounded buffer resources whatever K is."""
+    if K % 32 != 0 or K < 96 or M < 256 or N < 256 or N % 8 != 0:
+        raise _lib.EvpError(f"G4 weight-gradient problem out of contract: M={M} N={N} K={K} (K % 32 == 0, K >= 96, M, N >= 256, "
+                            "N % 8 == 0)")
 
 
 def _supertile_major(t, sm, sn):

@@ -199,7 +199,9 @@ int evp_gemm_grouped_tn_bf16(const void *problems, const void *items, int n_item
  * rows of dY of the same Linear -- computed from the A fragments already in registers (no second pass over dY). */
 int evp_gemm_grouped_tn_g4_bf16(const void *problems, const void *items, int n_items, void *stream);
 /* out[i] (+)= sum_s ws[s*numel + i], float32, numel % 4 == 0: reduction of split-K partials when a long-K problem was
- * entered into the grouped launch as several K-slice problems writing to a workspace (ConvViT stage 1: K = B*56*56). */
+ * entered into the grouped launch as several K-slice problems writing to a workspace (ConvViT stage 1: K = B*56*56).
+ * Every slice a G4 table receives satisfies the G4 K contract (K % 32 == 0, K >= 96): the planner folds a shorter last
+ * slice into the one before it and checks each G4 problem on the host (ops._check_g4_problem) before the table is staged. */
 int evp_sum_slices_f32(const float *ws, float *out, int n_slices, int64_t numel, int accumulate, void *stream);
 /* Tuning switches for A/B measurements (results are identical up to f32 summation order): 1 = LDS-DMA (buffer_load ... lds)
  * staging for bf16 (default), 2 = register staging; 10 = wide forward / data-gradient GEMMs on 128x128 tiles (default: the G4
