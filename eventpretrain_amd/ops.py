@@ -15,7 +15,7 @@ import numpy as np
 
 import torch
 
-from . import _lib
+from . import _lib, wgrad_plan
 from ._lib import (ACT_DGELU, ACT_DRELU, ACT_GELU, ACT_NONE, ACT_RELU, EVP_BF16, EVP_F32, GemmDesc, call, dt, ptr,
                    stream_ptr)
 
@@ -383,7 +383,7 @@ class _DeferredGrads:
                 and param.requires_grad and param.dtype == torch.float32 and param.is_contiguous())
 
     def wgrad(self, param, dy, x, n_out, k_in, rows, bias_param=None):
-        self.w.append((param, dy, x, n_out, k_in, rows, bias_param))
+        self.w.append(wgrad_plan.WgradProblem(param, dy, x, n_out, k_in, rows, bias_param))
         self.arm()
 
     def colsum(self, param, x2d):
@@ -467,8 +467,7 @@ class _DeferredGrads:
                 call("evp_sum_slices_f32", ws.data_ptr(), out.data_ptr(), ns, numel, acc, stream_ptr())
 
     def _build(self, n_chunks, static):
-        import numpy as np
-        w, b, self.w, self.b = self.w, self.b, [], []
+        w, b, self.w, self.b = [wgrad_plan.WgradProblem(*q) for q in self.w], self.b, [], []
         steps = []
 
         def table(key, arr, dev):
@@ -491,133 +490,60 @@ class _DeferredGrads:
                 self.flat_buffers.append(flat)  # parameters' .grad views are the only owners and zero_grad frees them
             return flat, {id(p_) for p_ in fresh}
 
-        if w:
-            dev = w[0][1].device
+        def target(param, fresh_ids):
+            gt, acc = self._target(param)
+            return gt, 0 if id(param) in fresh_ids else acc     # first write into the freshly allocated flat slice
 
-            def big_(it):       # long-K problems with >= 256-wide outputs go to the 256x256 G4 kernel (K % 32 == 0, K >= 96)
-                return _use_wgrad_g4 and it[5] % 32 == 0 and it[5] >= 96 and it[3] >= 256 and it[4] >= 256
-            # a bias gradient rides on its Linear's weight-gradient problem only in the 256x256 kernel; otherwise it joins
-            # the grouped column sums below
-            for it in w:
-                if it[6] is not None and not big_(it):
-                    b.append((it[6], it[1]))
-            # A parameter used by several autograd nodes of one backward (rec+con: masked AND dense forward) has several
-            # queued contributions. Tiles of different problems run concurrently, so contributions to the SAME gradient
-            # go to successive launches (round r holds every parameter's r-th contribution; normally one round).
-            rounds, count = [], {}
-            for item in w:
-                r = count.get(id(item[0]), 0)
-                count[id(item[0])] = r + 1
-                while len(rounds) <= r:
-                    rounds.append([])
-                rounds[r].append(item)
-            pdt = np.dtype([("A", "<u8"), ("B", "<u8"), ("C", "<u8"), ("M", "<i4"), ("N", "<i4"), ("K", "<i4"), ("lda", "<i4"),
-                            ("ldb", "<i4"), ("ldc", "<i4"), ("acc", "<i4"), ("cacc", "<i4"), ("colsum", "<u8")])
-            for r, batch in enumerate(rounds):
-                # per round: the 256x256 ring kernel (in n_chunks launches when a plan is built) and the 128x128 kernel;
-                # inside a launch the longest-K tiles are listed first
-                big = sorted([it for it in batch if big_(it)], key=lambda it: -it[5])
-                small = sorted([it for it in batch if not big_(it)], key=lambda it: -it[5])
-                groups = []
-                if big:
-                    k = max(1, min(n_chunks if r == 0 else 1, len(big)))
-                    work = np.cumsum([float(it[3]) * it[4] * it[5] for it in big])
-                    cuts = [0] + [int(np.searchsorted(work, work[-1] * (c + 1) / k, side="left")) + 1 for c in range(k - 1)] + [len(big)]
-                    cuts = sorted(set(min(max(c, 0), len(big)) for c in cuts))
-                    for c in range(len(cuts) - 1):
-                        if cuts[c + 1] > cuts[c]:
-                            part_ = big[cuts[c]:cuts[c + 1]]
-                            groups.append(("w256r%dc%d" % (r, c), part_, 256, "evp_gemm_grouped_tn_g4_bf16"))
-                if small:
-                    groups.append(("w128r%d" % r, small, 128, "evp_gemm_grouped_tn_bf16"))
-                for tag, part, T_, entry in groups:
-                    # A problem with few output tiles and a very long K (ConvViT stage 1: 256x256 outputs, K = B*56*56)
-                    # would keep one workgroup busy for the whole launch: cut its K into slices that run as separate
-                    # problems into a workspace and are summed afterwards. The bias then takes the column-sum launch.
-                    def n_slices_(it):
-                        tiles = ((it[3] + T_ - 1) // T_) * ((it[4] + T_ - 1) // T_)
-                        return int(min(64, it[5] // 8192)) if (tiles <= 32 and it[5] >= 32768 and (it[3] * it[4]) % 4 == 0) else 1
-                    for it in part:
-                        if it[6] is not None and T_ == 256 and n_slices_(it) > 1:
-                            b.append((it[6], it[1]))
-                    flat, fresh_ids = alloc_fresh([it[0] for it in part] +
-                                                  [it[6] for it in part if it[6] is not None and T_ == 256 and n_slices_(it) == 1],
-                                                  dev, zeroed=False)
-                    rows_, items, post = [], [], []
-                    for (param, dy, x, n_out, k_in, rows, bias_param) in part:
-                        gt, acc = self._target(param)
-                        if id(param) in fresh_ids:
-                            acc = 0                  # first write into the freshly allocated flat slice
-                        ns = n_slices_((param, dy, x, n_out, k_in, rows, bias_param))
-                        tm, tn = (n_out + T_ - 1) // T_, (k_in + T_ - 1) // T_
-                        if ns > 1:
-                            kper = ((rows // 64 + ns - 1) // ns) * 64
-                            ns = (rows + kper - 1) // kper
-                            if T_ == 256 and rows - (ns - 1) * kper < 96:
-                                ns -= 1              # a G4 slice needs K >= 96: the short tail joins the slice before it
-                            numel = n_out * k_in
-                            ws = torch.empty(ns * numel, dtype=torch.float32, device=dev)
-                            for sidx in range(ns):
-                                k0 = sidx * kper
-                                kk = rows - k0 if sidx == ns - 1 else kper
-                                rows_.append((dy.data_ptr() + k0 * n_out * 2, x.data_ptr() + k0 * k_in * 2, ws.data_ptr() + sidx * numel * 4,
-                                              n_out, k_in, kk, n_out, k_in, k_in, 0, 0, 0, tm, tn))
-                            post.append((ws, gt, ns, numel, acc))
-                            continue
-                        cs_ptr, cs_acc = 0, 0
-                        if bias_param is not None and T_ == 256:
-                            bt, cs_acc = self._target(bias_param)
-                            if id(bias_param) in fresh_ids:
-                                cs_acc = 0
-                            cs_ptr = bt.data_ptr()
-                        rows_.append((dy.data_ptr(), x.data_ptr(), gt.data_ptr(), n_out, k_in, rows, n_out, k_in, k_in, acc, cs_acc, cs_ptr, tm, tn))
-                    rows_.sort(key=lambda r_: -r_[5])           # longest K first
-                    if T_ == 256:
-                        for r_ in rows_:
-                            _check_g4_problem(r_[3], r_[4], r_[5])
-                    probs = np.zeros(len(rows_), dtype=pdt)
-                    weights = []
-                    for i, r_ in enumerate(rows_):
-                        probs[i] = r_[:12]
-                        tm, tn = r_[12], r_[13]
-                        t = np.zeros((tn, tm, 4), dtype=np.int32)
-                        t[..., 0] = i
-                        t[..., 1] = np.arange(tm, dtype=np.int32)[None, :]
-                        t[..., 2] = np.arange(tn, dtype=np.int32)[:, None]
-                        if _wgrad_xcd_order and T_ == 256:
-                            t = _supertile_major(t, 2, 4)
-                        items.append(t.reshape(-1, 4))
-                        weights.append(np.full(tm * tn, float(r_[5]), dtype=np.float64))
-                    items = np.concatenate(items, 0)
-                    if _wgrad_xcd_order and T_ == 256:
-                        items = _deal_to_xcds(items, np.concatenate(weights))
-                    pt = table(tag + "p", probs.view(np.uint8), dev)
-                    it_ = table(tag + "i", items.view(np.uint8).reshape(-1), dev)
-                    steps.append(self._Step(entry, pt, it_, int(items.shape[0]), [flat] if flat is not None else [], [],
-                                            [(it[1], it[2]) for it in part], post))
-                    steps[-1].round = r
+        if w:
+            dev = w[0].dy.device
+            launches, listed = wgrad_plan.layout(w, n_chunks, _use_wgrad_g4, _wgrad_xcd_order)
+            b += [(q.bias, q.dy) for q in listed]
+            for ln in launches:
+                flat, fresh_ids = alloc_fresh([m.q.param for m in ln.members] +
+                                              [m.q.bias for m in ln.members if m.route.bias == "fused"], dev, zeroed=False)
+                # per member: address and accumulate flag of its gradient (or workspace) and of its fused bias gradient
+                dest, post = [], []
+                for q, route in ln.members:
+                    gt, acc = target(q.param, fresh_ids)
+                    cs_ptr, cs_acc = 0, 0
+                    if len(route.slices) > 1:
+                        numel = q.n_out * q.k_in
+                        ws = torch.empty(len(route.slices) * numel, dtype=torch.float32, device=dev)
+                        post.append((ws, gt, len(route.slices), numel, acc))
+                        gt, acc = ws, 0
+                    elif route.bias == "fused":
+                        bt, cs_acc = target(q.bias, fresh_ids)
+                        cs_ptr = bt.data_ptr()
+                    dest.append((gt.data_ptr(), acc, cs_ptr, cs_acc))
+                addr = []
+                for row in ln.rows:
+                    q = ln.members[row.src].q
+                    if ln.entry == wgrad_plan.G4:
+                        _check_g4_problem(q.n_out, q.k_in, row.k)
+                    c_ptr, acc, cs_ptr, cs_acc = dest[row.src]
+                    addr.append((q.dy.data_ptr() + row.k0 * q.n_out * 2, q.x.data_ptr() + row.k0 * q.k_in * 2,
+                                 c_ptr + max(row.ws_slice, 0) * q.n_out * q.k_in * 4, acc, cs_acc, cs_ptr))
+                for name, column in zip(("A", "B", "C", "acc", "cacc", "colsum"), zip(*addr)):
+                    ln.probs[name] = column
+                pt = table(ln.tag + "p", ln.probs.view(np.uint8), dev)
+                it = table(ln.tag + "i", ln.items.view(np.uint8).reshape(-1), dev)
+                steps.append(self._Step(ln.entry, pt, it, int(ln.items.shape[0]), [flat] if flat is not None else [], [],
+                                        [(m.q.dy, m.q.x) for m in ln.members], post))
+                steps[-1].round = ln.round
         if b:
             dev = b[0][1].device
-            probs = np.zeros(len(b), dtype=np.dtype([("x", "<u8"), ("out", "<u8"), ("M", "<i8"), ("N", "<i4"), ("ld", "<i4"),
-                                                      ("dtype", "<i4"), ("pad", "<i4")]))
-            items = []
+            probs = np.zeros(len(b), dtype=wgrad_plan.COLSUM_DT)
             # fresh bias gradients are slices of ONE flat buffer zeroed by one memset (they accumulate with atomics)
-            flat, _ = alloc_fresh([t_[0] for t_ in b], dev, zeroed=True)
+            flat, _ = alloc_fresh([param for param, _ in b], dev, zeroed=True)
             for i, (param, x2d) in enumerate(b):
                 M, N = x2d.shape
                 gt, acc = self._target(param)
                 probs[i] = (x2d.data_ptr(), gt.data_ptr(), M, N, x2d.stride(0), dt(x2d), 0)
-                cb, rs = (N + 127) // 128, (M + 255) // 256
-                t = np.zeros((rs, cb, 4), dtype=np.int32)
-                t[..., 0] = i
-                t[..., 1] = np.arange(cb, dtype=np.int32)[None, :]
-                t[..., 2] = np.arange(rs, dtype=np.int32)[:, None]
-                items.append(t.reshape(-1, 4))
-            items = np.concatenate(items, 0)
+            items = wgrad_plan.colsum_items([x2d.shape for _, x2d in b])
             pt = table("bp", probs.view(np.uint8), dev)
             it = table("bi", items.view(np.uint8).reshape(-1), dev)
-            st = self._Step("evp_colsum_grouped", pt, it, int(items.shape[0]), [flat] if flat is not None else [],
-                            [flat] if (static and flat is not None) else [], [t_[1] for t_ in b])
+            st = self._Step(wgrad_plan.COLSUM, pt, it, int(items.shape[0]), [flat] if flat is not None else [],
+                            [flat] if (static and flat is not None) else [], [x2d for _, x2d in b])
             # in a plan the short column-sum launch goes first: its all-reduce then hides under the first GEMM chunk
             if static:
                 steps.insert(0, st)
@@ -627,45 +553,9 @@ class _DeferredGrads:
 
 
 def _check_g4_problem(M, N, K):
-    """The G4 grouped body's contract (include/evtpretrain.h): its tables live on the device, where nothing checks them,
-    and its prologue consumes three 32-row stages with unbounded buffer resources whatever K is."""
-    if K % 32 != 0 or K < 96 or M < 256 or N < 256 or N % 8 != 0:
-        raise _lib.EvpError(f"G4 weight-gradient problem out of contract: M={M} N={N} K={K} (K % 32 == 0, K >= 96, M, N >= 256, "
-                            "N % 8 == 0)")
-
-
-def _supertile_major(t, sm, sn):
-    """[tn, tm, 4] tile grid -> the same tiles listed super-tile by super-tile (sn x sm tiles each, tile_m fastest inside):
-    the 8 tiles of a 2 x 4 super-tile read 2 A panels and 4 B panels between them instead of 16."""
-    tn, tm = t.shape[0], t.shape[1]
-    out = []
-    for n0 in range(0, tn, sn):
-        for m0 in range(0, tm, sm):
-            out.append(t[n0:n0 + sn, m0:m0 + sm].reshape(-1, 4))
-    return np.concatenate(out, 0)
-
-
-def _deal_to_xcds(items, work, n_xcd=8):
-    """Workgroups b and b + 8 run on the same XCD (one L2 each; MI355X_MICROARCH.md, workgroup dispatch) and an XCD's CUs
-    take its workgroups in launch order. Cut the item sequence (super-tile major, longest K first) into 8 CONTIGUOUS runs of
-    equal estimated work (tiles x K) and interleave them, items[8 k + x] = run_x[k], so that the ~32 tiles an XCD runs at any
-    moment are neighbouring super-tiles of one problem -- they advance through K in lockstep and find each other's panels in
-    their L2 instead of re-reading them through the Infinity Cache (2.9x over-fetch measured in round 1). Short runs are
-    padded with prob = -1 items, which the kernels skip. Placement is speed only: any assignment gives the same result."""
-    n = items.shape[0]
-    if n < 4 * n_xcd:
-        return items
-    cum = np.cumsum(work)
-    cuts = [0] + [int(np.searchsorted(cum, cum[-1] * (x + 1) / n_xcd, side="left")) + 1 for x in range(n_xcd - 1)] + [n]
-    cuts = [min(max(c, 0), n) for c in cuts]
-    for i in range(1, len(cuts)):
-        cuts[i] = max(cuts[i], cuts[i - 1])
-    runs = [items[cuts[x]:cuts[x + 1]] for x in range(n_xcd)]
-    longest = max(r.shape[0] for r in runs)
-    out = np.full((longest, n_xcd, 4), -1, dtype=np.int32)
-    for x, r in enumerate(runs):
-        out[:r.shape[0], x] = r
-    return out.reshape(-1, 4)
+    """Host check of wgrad_plan.g4_ok before a G4 table is staged: on the device nothing checks it."""
+    if not wgrad_plan.g4_ok(M, N, K):
+        raise _lib.EvpError(f"G4 weight-gradient problem out of contract: M={M} N={N} K={K} ({wgrad_plan.G4_CONTRACT})")
 
 
 _wgrad_xcd_order = os.environ.get("EVP_WGRAD_XCD", "1") != "0"
@@ -679,7 +569,6 @@ def set_wgrad_g4(flag):
     _use_wgrad_g4 = bool(flag)
 
 
-
 def set_wgrad_xcd_order(flag):
     """A/B switch: XCD-aware order of the grouped 256x256 weight-gradient items (default) or the plain problem-major list."""
     global _wgrad_xcd_order
@@ -687,6 +576,8 @@ def set_wgrad_xcd_order(flag):
 
 
 _deferred = _DeferredGrads()
+
+
 def set_deferred_grads(flag):
     """A/B switch: grouped end-of-backward weight/bias gradients (default) or one GEMM / column sum per layer."""
     _deferred.enabled = bool(flag)

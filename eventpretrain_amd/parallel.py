@@ -2,7 +2,7 @@
 xGMI. Replaces the reference's DistributedDataParallel wrap (main_pretrain.py:319; collective C1 in SURVEY.md 2.2).
 
 Where the gradients live decides the shape of the collective:
-  * weight / bias gradients are written by the deferred grouped launches (ops._DeferredGrads) straight into a few
+  * weight / bias gradients are written by the deferred grouped launches (planned by wgrad_plan, bound by ops._DeferredGrads) straight into a few
     large flat f32 buffers (`param.grad` are views) -> they are SUM-all-reduced IN PLACE, no packing pass;
   * the remaining small gradients (LayerNorm / BatchNorm affine, mask token) are packed into one small flat bucket
     with a multi-tensor copy and reduced with a single call.
@@ -53,7 +53,7 @@ class _Plan:
 
 class OverlappedPlan:
     """HIP-graph data-parallel step, gradient part: the deferred weight-gradient work was kept OUT of the captured
-    forward+backward graph and cut into chunks (ops.build_deferred_plan); run() launches chunk c and immediately issues the
+    forward+backward graph and cut into chunks (ops.build_deferred_plan, chunk cuts by wgrad_plan.layout); run() launches chunk c and immediately issues the
     asynchronous all-reduce of the flat buffer chunk c-... wrote, so RCCL (on its own stream, ordered after the chunk by
     the event torch.distributed records at the call) moves chunk c over xGMI while chunk c+1's GEMMs run. Only the last
     chunk's all-reduce is exposed. The small gradients autograd produced inside the graph go through the packed bucket

@@ -1,5 +1,6 @@
-"""Shared by the CPU and GPU tests of the deferred weight / bias gradients (ops._DeferredGrads): a float64 interpreter of the
-grouped launch tables the planner builds, and the per-layer problem lists of the benchmarked models.
+"""Shared by the CPU and GPU tests of the deferred weight / bias gradients (eventpretrain_amd/wgrad_plan.py lays the launches
+out, ops._DeferredGrads binds them): a float64 interpreter of the grouped launch tables they build (byte layout and entry names
+taken from the planner; contracts and tile geometry stated here), and the per-layer problem lists of the benchmarked models.
 
 The interpreter follows the C ABI (include/evtpretrain.h) of the four entries a plan step launches:
   evp_gemm_grouped_tn_bf16 / evp_gemm_grouped_tn_g4_bf16: C[m][n] (+)= sum_k A[k][m] B[k][n] per 128 / 256 output tile,
@@ -18,13 +19,8 @@ import numpy as np
 import torch
 
 from eventpretrain_amd import _lib
+from eventpretrain_amd.wgrad_plan import COLSUM, G4, T128, COLSUM_DT as CDT, PROBLEM_DT as PDT
 
-PDT = np.dtype([("A", "<u8"), ("B", "<u8"), ("C", "<u8"), ("M", "<i4"), ("N", "<i4"), ("K", "<i4"), ("lda", "<i4"), ("ldb", "<i4"),
-                ("ldc", "<i4"), ("acc", "<i4"), ("cacc", "<i4"), ("colsum", "<u8")])
-CDT = np.dtype([("x", "<u8"), ("out", "<u8"), ("M", "<i8"), ("N", "<i4"), ("ld", "<i4"), ("dtype", "<i4"), ("pad", "<i4")])
-G4 = "evp_gemm_grouped_tn_g4_bf16"
-T128 = "evp_gemm_grouped_tn_bf16"
-COLSUM = "evp_colsum_grouped"
 TILE = {G4: 256, T128: 128}
 
 

@@ -1,4 +1,4 @@
-"""The deferred bf16 weight / bias gradient planner (ops._DeferredGrads.build_plan) on the host, no GPU: its grouped launch
+"""The deferred bf16 weight / bias gradient planner (wgrad_plan.layout bound by ops._DeferredGrads.build_plan) on the host, no GPU: its grouped launch
 tables are run by a float64 interpreter of the four entries' ABI (tests/deferred_plan.py).
 
 * Sweep: the per-layer problem lists of every benchmarked model (taken from the instantiated modules), batches 1-256, every
@@ -10,7 +10,7 @@ import numpy as np
 import pytest
 import torch
 
-from eventpretrain_amd import _lib, ops
+from eventpretrain_amd import _lib, ops, wgrad_plan
 
 import deferred_plan as dp
 
@@ -75,6 +75,21 @@ def test_g4_contract_is_checked_on_the_host():
     for M, N, K in [(256, 256, 32), (256, 256, 64), (256, 256, 112), (255, 256, 96), (256, 248, 96), (256, 260, 96)]:
         with pytest.raises(_lib.EvpError):
             ops._check_g4_problem(M, N, K)
+
+
+def test_route_is_decided_once_and_consistent():
+    """Routing of one problem needs no tensors: a fused bias implies the 256 tile and one slice, every G4 slice meets the
+    contract, and the slices partition the rows."""
+    for n_out, k_in in [(1536, 384), (256, 256), (768, 768), (128, 64), (264, 1032), (256, 136)]:
+        for rows in list(range(1, 400)) + [b * 784 for b in range(1, 257)] + [b * 3136 for b in (8, 42, 64, 256)]:
+            for g4 in (True, False):
+                r = wgrad_plan.route(n_out, k_in, rows, True, g4)
+                assert r.bias == ("fused" if r.tile == 256 and len(r.slices) == 1 else "listed")
+                assert r.tile == (256 if g4 and rows % 32 == 0 and rows >= 96 and min(n_out, k_in) >= 256 else 128)
+                assert [k0 for k0, _ in r.slices] == [sum(k for _, k in r.slices[:i]) for i in range(len(r.slices))]
+                assert sum(k for _, k in r.slices) == rows
+                assert r.tile == 128 or all(k % 32 == 0 and k >= 96 for _, k in r.slices), (n_out, k_in, rows, r)
+                assert wgrad_plan.route(n_out, k_in, rows, False, g4) == r._replace(bias="none")
 
 
 # ------------------------------------------------------------------------------------------------------ numeric cases
