@@ -2,6 +2,11 @@
 // norm (utils/misc.py:303-315). One launch covers every parameter: a host-built chunk table maps each workgroup
 // to (tensor, offset); weight decay / lr scale are per tensor. The step also writes the bf16 shadow of each weight
 // that the next forward's MFMA GEMMs read, so no separate cast pass touches the 112 M parameters.
+// Gradient clipping (torch.nn.utils.clip_grad_norm_, utils/misc.py:289-290) stays on the device: evp_grad_clip_multi
+// reads every gradient once (16 B per lane), reduces wave -> LDS -> one partial per chunk -> one workgroup, and the thread
+// that finishes the reduction multiplies the coefficient into dev_hyper[2], which adamw_kernel applies as it reads each
+// gradient. No pass writes the gradients, no float atomics (bit-identical from replay to replay), no host decision:
+// the clipped step can live in a captured HIP graph.
 #include "evp_common.h"
 
 namespace {
@@ -84,6 +89,55 @@ __global__ __launch_bounds__(1024) void sqrt_sum(const float *part, int n, float
   if (threadIdx.x == 0) out[0] = sqrtf(s);
 }
 
+// Sum of squares of one chunk, 16 B per lane. The split is by ADDRESS (a gradient may be a view that starts off a 16-byte
+// boundary): scalar head up to the boundary, float4 body, scalar tail. Fixed summation order: the partial is reproducible.
+__global__ __launch_bounds__(256) void sumsq_chunks_v4(const float *const *grads, const int64_t *numel, const int32_t *chunk_tensor,
+                                                       const int64_t *chunk_offset, int chunk_elems, float *part) {
+  __shared__ float red[16];
+  const int t = chunk_tensor[blockIdx.x];
+  const int64_t off = chunk_offset[blockIdx.x];
+  int64_t cnt = numel[t] - off; if (cnt > chunk_elems) cnt = chunk_elems;
+  if (cnt < 0) cnt = 0;
+  const float *g = grads[t] + off;
+  int64_t head = (int64_t)(((16u - (unsigned)((uintptr_t)g & 15u)) & 15u) >> 2);
+  if (head > cnt) head = cnt;
+  const int64_t c4 = (cnt - head) >> 2;
+  const float4 *g4 = reinterpret_cast<const float4 *>(g + head);
+  float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
+#pragma unroll 4
+  for (int64_t i = threadIdx.x; i < c4; i += 256) {
+    const float4 v = g4[i];
+    s0 += v.x * v.x; s1 += v.y * v.y; s2 += v.z * v.z; s3 += v.w * v.w;
+  }
+  float s = (s0 + s1) + (s2 + s3);
+  if ((int64_t)threadIdx.x < head) s += g[threadIdx.x] * g[threadIdx.x];
+  for (int64_t i = head + c4 * 4 + threadIdx.x; i < cnt; i += 256) s += g[i] * g[i];
+  s = block_sum(s, red);
+  if (threadIdx.x == 0) part[blockIdx.x] = s;
+}
+// Final stage, one workgroup: the chunk partials are summed in double (fixed order), then the one thread that holds the sum
+// evaluates clip_grad_norm_'s coefficient in double and scales hyper[2] for the adamw_kernel launch behind it.
+__global__ __launch_bounds__(1024) void clip_final(const float *part, int n, double max_norm, float *hyper, float *out) {
+  __shared__ double red[16];
+  double s = 0.0;
+  for (int i = threadIdx.x; i < n; i += 1024) s += (double)part[i];
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double tot = 0.0;
+    for (int i = 0; i < 16; ++i) tot += red[i];
+    const float gs = hyper[2];
+    const float norm = sqrtf((float)tot) * gs;            // the norm of the gradient the optimizer applies (1 / world included)
+    const double c = max_norm / ((double)norm + 1e-6);
+    const double coef = c < 1.0 ? c : 1.0;                // min(1, c) as the host evaluates it
+    out[0] = norm;
+    out[1] = (float)coef;
+    hyper[2] = (float)((double)gs * coef);
+  }
+}
+
 }  // namespace
 
 extern "C" int evp_adamw_multi(float *const *params, const float *const *grads, float *const *exp_avg, float *const *exp_avg_sq,
@@ -114,5 +168,19 @@ extern "C" int evp_grad_norm_multi(const float *const *grads, const int64_t *num
   EVP_CHECK_LAUNCH("evp_grad_norm_multi");
   hipLaunchKernelGGL(sqrt_sum, dim3(1), dim3(1024), 0, s, workspace, n_chunks, out);
   EVP_CHECK_LAUNCH("evp_grad_norm_multi(final)");
+  return EVP_OK;
+}
+
+extern "C" int evp_grad_clip_multi(const float *const *grads, const int64_t *numel, const int32_t *chunk_tensor,
+                                   const int64_t *chunk_offset, int n_chunks, int chunk_elems, float *workspace, double max_norm,
+                                   float *hyper, float *out, void *stream) {
+  EVP_CHECK_ARG(grads && numel && chunk_tensor && chunk_offset && workspace && hyper && out, EVP_EINVAL, "evp_grad_clip_multi: null table");
+  EVP_CHECK_ARG(n_chunks > 0 && chunk_elems > 0, EVP_EINVAL, "evp_grad_clip_multi: bad chunking (n_chunks %d, chunk_elems %d)", n_chunks, chunk_elems);
+  EVP_CHECK_ARG(isfinite(max_norm) && max_norm > 0.0, EVP_EINVAL, "evp_grad_clip_multi: max_norm must be finite and positive (got %g)", max_norm);
+  hipStream_t s = (hipStream_t)stream;
+  hipLaunchKernelGGL(sumsq_chunks_v4, dim3(n_chunks), dim3(256), 0, s, grads, numel, chunk_tensor, chunk_offset, chunk_elems, workspace);
+  EVP_CHECK_LAUNCH("evp_grad_clip_multi");
+  hipLaunchKernelGGL(clip_final, dim3(1), dim3(1024), 0, s, (const float *)workspace, n_chunks, max_norm, hyper, out);
+  EVP_CHECK_LAUNCH("evp_grad_clip_multi(final)");
   return EVP_OK;
 }

@@ -7,6 +7,9 @@ executor runs a few eager steps (allocator and autograd warm-up, on the capture 
     N ranks: [forward + backward] -> weight-gradient GEMMs in chunks, each chunk's flat buffer all-reduced (RCCL, in
              place) while the next chunk computes -> [AdamW]
 
+(`clip_grad`: evp_grad_clip_multi sits in front of AdamW inside the same graph -- the norm and the coefficient never leave
+the device; with N ranks the global norm needs every buffer reduced, so the update is one launch after the last all-reduce.)
+
 and from then on a step is: copy the batch into the static input buffers, draw the mask noise into its static buffer,
 stage the optimizer's per-step scalars (lr, bias corrections) into the pinned table the graph's own H2D node re-reads,
 replay. Collectives stay outside the graphs. If capture fails the executor says so and keeps stepping eagerly.
@@ -14,6 +17,7 @@ replay. Collectives stay outside the graphs. If capture fails the executor says 
 Replaces nothing in the reference (its loop is eager PyTorch, trainer/pretrain/pr_trainer.py:20-76); it is the
 MI355X-side answer to "launch-bound inner loop -> HIP graph". `trainer.pretrain.pr_trainer.pr_rec_one_epoch(...,
 step_executor=...)` uses it when given one."""
+import contextlib
 import os
 
 import torch
@@ -120,15 +124,20 @@ class _GraphSeq:
 
 class GraphedStep:
     def __init__(self, model, optimizer, forward, static_inputs, noise_shape=None, generator=None, reducer=None,
-                 use_graph=True, warmup=2, wgrad_chunks=4, step_prepare=None, host_generator=None, backward_cut=None):
+                 use_graph=True, warmup=2, wgrad_chunks=4, step_prepare=None, host_generator=None, backward_cut=None, clip_grad=None):
         """forward(model, *static_inputs, noise) -> tuple whose first item is the loss. `static_inputs`: device tensors
         with the batch's shapes (overwritten by `step(...)` when new data is passed). `noise_shape`: (B, L) of the
         masking noise, or None when the model draws none (density masking, contrastive stage).
         `step_prepare(noise_cpu) -> bool` (models whose launch geometry depends on the noise: the Swin backbone's window
         plan, `SwinTransformer.enable_static_plan`): the noise is then drawn on the HOST (`host_generator`), handed to the
         hook before anything is launched and copied to the static device buffer; False = the captured graph cannot serve
-        this step, which then runs eagerly with the same noise."""
+        this step, which then runs eagerly with the same noise.
+        `clip_grad`: torch.nn.utils.clip_grad_norm_(parameters, clip_grad) in front of every update (reference utils/misc.py:289-290),
+        on the device (FusedAdamW.max_grad_norm); `grad_norm` then holds {pre-clip norm, coefficient} of the last step."""
         self.model, self.opt, self.forward, self.reducer = model, optimizer, forward, reducer
+        self.clip_grad = None if clip_grad is None else float(clip_grad)
+        if self.clip_grad is not None and not hasattr(optimizer, "max_grad_norm"):
+            raise ValueError("GraphedStep(clip_grad=...) needs a FusedAdamW (the clip runs on the device, inside the optimizer's launch)")
         # data-parallel form only: cut the backward at the encoder / decoder boundary (two graphs, the decoder's gradients all-reduced
         # under the encoder's backward). None = the environment's EVP_DP_BACKWARD_CUT (see _capture for the default and why).
         self.backward_cut = (os.environ.get("EVP_DP_BACKWARD_CUT", _DP_BACKWARD_CUT_DEFAULT) != "0") if backward_cut is None else bool(backward_cut)
@@ -212,9 +221,32 @@ class GraphedStep:
         out[0].backward()
         if self.reducer is not None:
             self.reducer.finish()
-        self.opt.step()
+        self._opt_step()
         self.opt.zero_grad(set_to_none=True)
         return out[0]
+
+    @contextlib.contextmanager
+    def _clipping(self):
+        """The optimizer clips to this executor's clip_grad while one of its own updates is launched or captured (the optimizer is
+        the caller's: outside the executor it keeps whatever max_grad_norm it had)."""
+        if self.clip_grad is None:
+            yield
+            return
+        saved, self.opt.max_grad_norm = self.opt.max_grad_norm, self.clip_grad
+        try:
+            yield
+        finally:
+            self.opt.max_grad_norm = saved
+
+    def _opt_step(self):
+        with self._clipping():
+            self.opt.step()
+
+    @property
+    def grad_norm(self):
+        """Static device tensor {pre-clip gradient norm, clip coefficient} of the last step (clip_grad set; with N ranks the norm
+        of the MEAN gradient, the same on every rank). Read it before the next step, like `loss`."""
+        return self.opt.last_grad_norm if self.clip_grad is not None else None
 
     # ------------------------------------------------------------------------------------------------ capture
     def _snapshot(self):
@@ -299,7 +331,8 @@ class GraphedStep:
                         out[0].backward()
                         if not self.multi:
                             self.opt.refresh(scalars=False)
-                            self.opt.launch()
+                            with self._clipping():
+                                self.opt.launch()        # (clip_grad: evp_grad_clip_multi, then AdamW)
                         self.loss = out[0].detach()
                         del out
                         seq.end()
@@ -335,12 +368,14 @@ class GraphedStep:
                     self.plan = self.reducer.make_overlapped_plan(self.wgrad_chunks, early_steps=early_steps)
                 # AdamW in parts, each launched as soon as its gradient buffer is reduced (the graph then only holds the
                 # H2D copies of the per-step scalar tables); one launch after the last all-reduce otherwise
-                self.parts = self.plan.streams is not None
+                # (clip_grad: the global norm needs EVERY buffer reduced before any update -- one launch, the clip in front of it)
+                self.parts = self.plan.streams is not None and self.clip_grad is None
                 g2 = torch.cuda.CUDAGraph()
                 with torch.cuda.graph(g2, stream=side, capture_error_mode="thread_local"):
                     self.opt.refresh()
                     if not self.parts:
-                        self.opt.launch()
+                        with self._clipping():
+                            self.opt.launch()
                 if self.parts:
                     with torch.cuda.stream(side):
                         self.plan.attach_optimizer(self.opt, [p for p in self.model.parameters() if p.requires_grad])
@@ -350,7 +385,8 @@ class GraphedStep:
                               else "hip-graph (fwd+bwd) + ") +
                              "%d weight-gradient chunks on two streams, each all-reduced (RCCL) while the next "
                              "computes, AdamW per reduced buffer" % self.wgrad_chunks) if self.parts else \
-                            ("hip-graph (fwd+bwd) + %d weight-gradient chunks overlapped with RCCL all-reduce + hip-graph (AdamW)" % self.wgrad_chunks)
+                            ("hip-graph (fwd+bwd) + %d weight-gradient chunks overlapped with RCCL all-reduce + hip-graph (%sAdamW)"
+                             % (self.wgrad_chunks, "clip to the norm of the mean gradient + " if self.clip_grad is not None else ""))
                 if fc is not None and (fc.post or fc.pre or len(seq.graphs) > 1):
                     self.note += " [forward collectives outside the graphs: %d splitting key all-gather(s), %d overlapped with the backward, " \
                                  "%d buffer broadcast(s)]" % (len(seq.graphs) - 1, len(fc.post), len(fc.pre))
@@ -458,7 +494,7 @@ class GraphedStep:
             out[0].backward()
             if self.reducer is not None:
                 self.reducer.finish()
-            self.opt.step()
+            self._opt_step()
             self.opt.zero_grad(set_to_none=True)
             return out[0].detach()
         return self._eager_fallback(list(inputs), noise)
@@ -479,7 +515,7 @@ class GraphedStep:
             # data-parallel form: every rank is here (the verdict was collective, or every rank met the same short batch), so the
             # reducer's all-reduces match; the mean rides on the optimizer's grad_scale as in the captured step
             self.reducer.finish()
-        self.opt.step()
+        self._opt_step()
         self.opt.zero_grad(set_to_none=True)
         torch.cuda.current_stream().synchronize()
         for p, g in self._static_grads:

@@ -5,6 +5,10 @@ Subclasses torch.optim.Optimizer only for the param_groups / state_dict plumbing
 Per-group `lr` (already multiplied by `lr_scale` by utils.lr_sched.adjust_learning_rate) and `weight_decay` are read
 every step. Gradient pointers are re-read every step (autograd may hand out new buffers); under HIP-graph capture use
 `refresh()` outside the graph and `launch()` inside it.
+
+`max_grad_norm` (None = off) clips on the device (torch.nn.utils.clip_grad_norm_, reference utils/misc.py:289-290):
+`launch()` then issues evp_grad_clip_multi in front of evp_adamw_multi, which leaves {pre-clip norm, coefficient} in
+`last_grad_norm` and the coefficient folded into the device-resident gradient scale of that one step.
 """
 import math
 
@@ -18,7 +22,7 @@ CHUNK = 16384
 
 
 class FusedAdamW(torch.optim.Optimizer):
-    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, grad_scale=1.0):
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, grad_scale=1.0, max_grad_norm=None):
         defaults = dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay)
         super().__init__(params, defaults)
         b = {tuple(g["betas"]) for g in self.param_groups}
@@ -26,6 +30,7 @@ class FusedAdamW(torch.optim.Optimizer):
         if len(b) != 1 or len(e) != 1:
             raise ValueError("FusedAdamW needs one (betas, eps) for all groups")
         self.grad_scale = float(grad_scale)
+        self.max_grad_norm = max_grad_norm       # an attribute, not a param_group entry: the checkpoint layout stays AdamW's
         self._step = 0
         self._tabs = None
         self._sig = None
@@ -71,6 +76,7 @@ class FusedAdamW(torch.optim.Optimizer):
             hyper=torch.zeros(4, dtype=torch.float32, device=dev),
             norm_ws=torch.empty(sum(len(c) for c in chunk_t), dtype=torch.float32, device=dev),
             norm_out=torch.empty(1, dtype=torch.float32, device=dev),
+            clip_out=torch.zeros(2, dtype=torch.float32, device=dev),      # {norm, coef} of the last clipped launch()
         )
         T["n_chunks"] = int(T["chunk_t"].numel())
         # pinned staging for the per-step refresh
@@ -164,10 +170,21 @@ class FusedAdamW(torch.optim.Optimizer):
                 st["exp_avg_sq"].zero_()
         self._step = 0
 
+    @property
+    def last_grad_norm(self):
+        """Static device tensor {pre-clip norm of the applied gradient, clip coefficient} written by the last launch() with
+        `max_grad_norm` set (a captured graph keeps writing this same tensor); None before the first refresh()."""
+        return None if self._tabs is None else self._tabs["clip_out"]
+
     def launch(self):
-        """Device side of a step (graph-capturable): one evp_adamw_multi over all chunks."""
+        """Device side of a step (graph-capturable): one evp_adamw_multi over all chunks; with `max_grad_norm` set,
+        evp_grad_clip_multi in front of it scales this step's device-resident gradient scale by the clip coefficient."""
         T = self._tabs
         b1, b2 = self.param_groups[0]["betas"]
+        if self.max_grad_norm is not None:
+            call("evp_grad_clip_multi", T["grads"].data_ptr(), T["numel"].data_ptr(), T["chunk_t"].data_ptr(),
+                 T["chunk_o"].data_ptr(), T["n_chunks"], CHUNK, T["norm_ws"].data_ptr(), float(self.max_grad_norm),
+                 T["hyper"].data_ptr(), T["clip_out"].data_ptr(), stream_ptr())
         call("evp_adamw_multi", T["params"].data_ptr(), T["grads"].data_ptr(), T["m"].data_ptr(), T["v"].data_ptr(),
              T["lp"].data_ptr(), T["numel"].data_ptr(), T["wd"].data_ptr(), T["lr"].data_ptr(), T["chunk_t"].data_ptr(),
              T["chunk_o"].data_ptr(), T["n_chunks"], CHUNK, 1.0, float(b1), float(b2), float(self.param_groups[0]["eps"]),
@@ -199,6 +216,9 @@ class FusedAdamW(torch.optim.Optimizer):
 
     def launch_part(self, i):
         """Device side of the update for part i of build_parts() (same kernel, that part's chunk table)."""
+        if self.max_grad_norm is not None:
+            raise _lib.EvpError("launch_part: max_grad_norm is set -- the global norm needs every gradient buffer reduced before "
+                                "any update; use launch()")
         part = self._parts[i]
         if part is None:
             return

@@ -28,23 +28,26 @@ def auto_ft_step_executor(args, model, optimizer, loss_scaler, batch_tensors):
     """The fine-tuning step (dense backbone -> token mean -> head -> cross entropy -> backward -> FusedAdamW) captured once as a HIP
     graph, as trainer.pretrain.pr_trainer.auto_step_executor does for the pre-training loops. The stochastic
     regularisers of the recipe replay correctly: the DropPath draws and the dropout keys come from torch's device generator, which
-    advances under replay (ops.draw_block_drop / draw_drop_seed). Returns None where the captured form cannot stand in: gradient
-    accumulation, backward off, gradient clipping (its coefficient is a host decision on the gradient norm), an optimizer that is
-    not FusedAdamW, a CPU device, or `args.graph_step = False`."""
+    advances under replay (ops.draw_block_drop / draw_drop_seed). `args.clip_grad` (the reference's default recipe: --clip_grad 5) is
+    captured with the step: norm, coefficient and the scaled update stay on the device (evp_grad_clip_multi); a changed value
+    re-captures. Returns None where the captured form cannot stand in: gradient accumulation, backward off, an optimizer that is not
+    FusedAdamW, a CPU device, or `args.graph_step = False`."""
     from ...engine import GraphedStep
     from ...optim import FusedAdamW
-    if not getattr(args, "graph_step", True) or args.accum_iter != 1 or not args.backward or getattr(args, "clip_grad", None) is not None:
+    if not getattr(args, "graph_step", True) or args.accum_iter != 1 or not args.backward:
         return None
     if not str(args.device).startswith("cuda") or not isinstance(optimizer, FusedAdamW) or "forward" in vars(model):
         return None
     x, y = batch_tensors
-    key = (id(optimizer), "loss_cls", tuple(x.shape), tuple(y.shape), str(ops.get_compute_dtype()))
+    clip = getattr(args, "clip_grad", None)
+    clip = None if clip is None else float(clip)
+    key = (id(optimizer), "loss_cls", tuple(x.shape), tuple(y.shape), str(ops.get_compute_dtype()), clip)
     cached = getattr(model, "_evp_auto_executor", None)
-    if cached is not None and (cached[0] == key or (cached[0][:2] == key[:2] and cached[0][4] == key[4])):
+    if cached is not None and (cached[0] == key or (cached[0][:2] == key[:2] and cached[0][4:] == key[4:])):
         return cached[1]
     smoothing = float(getattr(args, "smoothing", 0) or 0)
     fwd = lambda m, x_, y_, noise: (ops.CrossEntropyFn.apply(m(x_)[-2], y_, smoothing),)
-    ex = GraphedStep(model, optimizer, fwd, [x.clone(), y.clone()], reducer=getattr(loss_scaler, "reducer", None))
+    ex = GraphedStep(model, optimizer, fwd, [x.clone(), y.clone()], reducer=getattr(loss_scaler, "reducer", None), clip_grad=clip)
     model._evp_auto_executor = (key, ex)
     return ex
 
@@ -105,8 +108,9 @@ def _graphed_epoch(args, model, data_loader, optimizer, epoch, loss_scaler, log_
     model.train(True)
     cached = getattr(model, "_evp_auto_executor", None)
     if cached is not None and cached[0][:2] == (id(optimizer), "loss_cls") and cached[0][4] == str(ops.get_compute_dtype()):
-        ex = cached[1]                     # built by an earlier epoch: no need to look at a batch first
-        if auto_ft_step_executor(args, model, optimizer, loss_scaler, tuple(ex.inputs)) is not ex:
+        # built by an earlier epoch: no need to look at a batch first (a changed clip_grad re-captures on the same static inputs)
+        ex = auto_ft_step_executor(args, model, optimizer, loss_scaler, tuple(cached[1].inputs))
+        if ex is None:
             return None
     else:
         it0 = iter(data_loader)

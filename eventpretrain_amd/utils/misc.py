@@ -216,22 +216,23 @@ class NativeScalerWithGradNormCount:
         gs = ensure_mean_grad_scale(optimizer, reducer, "NativeScalerWithGradNormCount")
         if reducer is not None:
             reducer.finish()
+        from ..optim import FusedAdamW
+        if clip_grad is not None and isinstance(optimizer, FusedAdamW):
+            # torch.nn.utils.clip_grad_norm_(parameters, clip_grad) (reference utils/misc.py:289-290): every gradient times
+            # min(1, clip / (total_norm + 1e-6)). FusedAdamW computes the norm and the coefficient on the device
+            # (evp_grad_clip_multi) and folds the coefficient into the gradient scale its kernel applies as it reads each
+            # gradient: no pass over the gradients, no read-back. The returned norm is the pre-clip total norm of the
+            # gradient the optimizer applies (the mean over ranks), as clip_grad_norm_ returns -- a device scalar.
+            saved = optimizer.max_grad_norm
+            optimizer.max_grad_norm = float(clip_grad)
+            try:
+                optimizer.step()
+            finally:
+                optimizer.max_grad_norm = saved
+            return optimizer.last_grad_norm[0]
         norm = get_grad_norm_(parameters, optimizer=optimizer)
         norm = norm * gs                     # the norm of the gradient the optimizer applies (the mean over ranks; 1 without a reducer)
         if clip_grad is not None:
-            # torch.nn.utils.clip_grad_norm_(parameters, clip_grad) (reference utils/misc.py:289-290): every gradient times
-            # min(1, clip / (total_norm + 1e-6)). The factor rides on FusedAdamW's grad_scale for this step (the kernel
-            # multiplies each gradient by it as it reads it) instead of a pass over the gradients; the returned norm is
-            # the pre-clip total norm, as clip_grad_norm_ returns.
-            coef = min(1.0, float(clip_grad) / (float(norm) + 1e-6))
-            if hasattr(optimizer, "grad_scale"):
-                saved = optimizer.grad_scale
-                optimizer.grad_scale = saved * coef
-                try:
-                    optimizer.step()
-                finally:
-                    optimizer.grad_scale = saved
-                return norm
             torch.nn.utils.clip_grad_norm_(parameters, clip_grad)
         optimizer.step()
         return norm

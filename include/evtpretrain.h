@@ -368,6 +368,16 @@ int evp_adamw_multi(float *const *params, const float *const *grads, float *cons
 int evp_grad_norm_multi(const float *const *grads, const int64_t *numel, const int32_t *chunk_tensor,
                         const int64_t *chunk_offset, int n_chunks, int chunk_elems, float *workspace, float *out,
                         void *stream);
+/* utils/misc.py:289-290 (torch.nn.utils.clip_grad_norm_(parameters, clip_grad)) without a host decision. In stream order:
+ * s = sum of g^2 over every chunk; norm = sqrtf(s) * hyper[2] (hyper = evp_adamw_multi's dev_hyper, whose [2] holds the
+ * gradient scale, 1 / world under data parallelism: the norm of the gradient the optimizer applies); coef =
+ * min(1, max_norm / (norm + 1e-6)) in double; out float32 [2] = {norm (pre-clip, what clip_grad_norm_ returns), coef};
+ * hyper[2] = (float)((double)hyper[2] * coef), which the evp_adamw_multi launch behind it in the same stream applies as it
+ * reads each gradient -- the gradients themselves are only read, once. hyper must be uploaded afresh for every step.
+ * Two launches, no float atomics: bit-identical from call to call. workspace float32 [n_chunks]. max_norm finite, > 0. */
+int evp_grad_clip_multi(const float *const *grads, const int64_t *numel, const int32_t *chunk_tensor,
+                        const int64_t *chunk_offset, int n_chunks, int chunk_elems, float *workspace, double max_norm,
+                        float *hyper, float *out, void *stream);
 
 /* ------------------------------------------------------------------------------------------------ K13 BatchNorm on tokens
  * mlp_head.py:13,18 applied as pr_hub_model.py:223-237 does: per-channel batch statistics over the B*L rows of
