@@ -141,14 +141,10 @@ def layernorm_fwd(x, gamma, beta, eps, out_dtype, x2=None, x3=None):
     return y, mean, rstd
 
 
-# Side information that travels with a residual-stream gradient from the LayerNorm backward that produced it to the
-# transformer block that consumes it next (autograd hands the tensor over, not these): its bf16 copy (the next GEMM's
-# operand, written by the same kernel) and the per-block column sums of it (the proj / fc2 bias gradient). Keyed by the
-# data pointer and validated by (a) a weak reference to the producing tensor -- a dead producer means the address may have
-# been reused -- and (b) its version counter, which views share: where a tensor has several consumers autograd SUMS the
-# incoming gradients and may do so in place into the first arrival, which keeps the pointer and changes the values. A handful
-# of entries at most.
-_grad_side = {}
+# Side record of a residual-stream gradient, set as an attribute on the tensor by the LayerNorm backward that made it: its
+# bf16 copy (the next GEMM's operand, written by the same kernel), the per-block column sums of it (the proj / fc2 bias
+# gradient) and the version it describes. Autograd hands the tensor object itself (or a view of it) to the one consumer; a
+# gradient that autograd summed from several is a new tensor without the record, or an old one whose version has moved.
 _use_grad_side = os.environ.get("EVP_GRAD_SIDE", "1") != "0"
 
 
@@ -160,52 +156,65 @@ def set_grad_side(flag):
 
 
 def _side_put(dx, lp, colsum_part):
-    import weakref
-    for k in [k for k, v in _grad_side.items() if v[0]() is None]:
-        del _grad_side[k]
-    while len(_grad_side) >= 8:
-        _grad_side.pop(next(iter(_grad_side)))
-    _grad_side[dx.data_ptr()] = (weakref.ref(dx), dx.numel(), lp, colsum_part, dx._version)
+    dx._evp_side = (lp, colsum_part, dx._version)
 
 
 def _side_take(g):
-    ent = _grad_side.pop(g.data_ptr(), None)
-    if ent is None or ent[0]() is None or ent[1] != g.numel() or not g.is_contiguous() or g._version != ent[4]:
+    """(bf16 copy, column-sum partials) of exactly `g`, once; (None, None) without a record that still describes it."""
+    t = g if hasattr(g, "_evp_side") else g._base           # the block below returns g0.view(B, N, D): look on the base too
+    rec = getattr(t, "_evp_side", None)
+    if rec is None:
         return None, None
-    return ent[2], ent[3]
+    del t._evp_side                                         # one use: the bf16 copy is not pinned beyond it
+    lp, colsum_part, version = rec
+    if version != g._version or not g.is_contiguous() or g.numel() != t.numel() or g.data_ptr() != t.data_ptr():
+        return None, None
+    return lp, colsum_part
+
+
+def _norm_defer(params, D):
+    return params is not None and D % 8 == 0 and _deferred.can_defer(params[0]) and _deferred.can_defer(params[1])
+
+
+def _norm_grads(params, D, M, device, n_partial_rows=2):
+    """Where a LayerNorm backward kernel over M rows leaves d gamma / d beta: -> (ws, dgamma, dbeta, finish). The kernel
+    writes per-block partials into ws [nblk, n_partial_rows * D] (d gamma | d beta | ...). With `params=(weight, bias)` leaf
+    Parameters that can take deferred gradients, dgamma and dbeta are None (the kernel skips its own reduction) and
+    finish(), called after the kernel, queues the two partial rows for the step's grouped column-sum launch."""
+    defer = _norm_defer(params, D)
+    ws = torch.empty(call("evp_layernorm_bwd_nblk", M), n_partial_rows * D, dtype=torch.float32, device=device)
+    dgamma = dbeta = None
+    if not defer:
+        dgamma = torch.empty(D, dtype=torch.float32, device=device)
+        dbeta = torch.empty(D, dtype=torch.float32, device=device)
+
+    def finish():
+        if defer:
+            _deferred.colsum(params[0], ws[:, :D])
+            _deferred.colsum(params[1], ws[:, D:2 * D])
+    return ws, dgamma, dbeta, finish
 
 
 def layernorm_bwd(dy, x, gamma, mean, rstd, gres=None, x2=None, x3=None, want_lp=False, params=None, side=False):
-    """Returns (dx f32, dx_lp bf16|None, dgamma, dbeta). With `params=(weight, bias)` leaf Parameters that may take
-    deferred gradients, the per-block dgamma/dbeta partials are queued for the step's grouped column-sum launch
-    instead of being reduced by a kernel of their own, and (dx, dx_lp, None, None) is returned. `side` (deferred mode
-    only): the kernel also leaves per-block column sums of dx, and (bf16 copy, those partials) are registered for whoever
-    receives dx as its incoming gradient (_side_take)."""
+    """Returns (dx f32, dx_lp bf16|None, dgamma, dbeta); dgamma / dbeta are None where `params` take them deferred (see
+    _norm_grads). `side` (deferred mode only): the kernel also leaves per-block column sums of dx, and (bf16 copy, those
+    partials) are recorded on dx for whoever receives it as its incoming gradient (_side_take)."""
     M, D = x.shape
     dx = torch.empty(M, D, dtype=torch.float32, device=x.device)
     dx_lp = torch.empty(M, D, dtype=torch.bfloat16, device=x.device) if want_lp else None
-    nb = call("evp_layernorm_bwd_nblk", M)
-    defer = (params is not None and D % 8 == 0 and _deferred.can_defer(params[0]) and _deferred.can_defer(params[1]))
     # (the three-partial-row kernel keeps 4 rows x 3 D floats in LDS: D <= 3412; wider rows take the plain kernel below and the
     # consumer of dx casts / column-sums it itself)
-    if defer and side and _use_grad_side and 4 * 3 * D * 4 <= 160 * 1024:
-        ws = torch.empty(nb, 3 * D, dtype=torch.float32, device=x.device)
+    cs = side and _use_grad_side and 4 * 3 * D * 4 <= 160 * 1024 and _norm_defer(params, D)
+    ws, dgamma, dbeta, finish = _norm_grads(params, D, M, x.device, 3 if cs else 2)
+    if cs:
         call("evp_layernorm_bwd_cs", ptr(_chk(dy)), dt(dy), ptr(x), ptr(x2), ptr(x3), ptr(gamma), ptr(mean), ptr(rstd),
              ptr(gres), M, D, ptr(dx), ptr(dx_lp), ptr(ws), stream_ptr())
-        _deferred.colsum(params[0], ws[:, :D])
-        _deferred.colsum(params[1], ws[:, D:2 * D])
+    else:
+        call("evp_layernorm_bwd", ptr(_chk(dy)), dt(dy), ptr(x), ptr(x2), ptr(x3), ptr(gamma), ptr(mean), ptr(rstd),
+             ptr(gres), M, D, ptr(dx), ptr(dx_lp), ptr(dgamma), ptr(dbeta), ptr(ws), stream_ptr())
+    finish()
+    if cs:
         _side_put(dx, dx_lp, ws[:, 2 * D:])
-        return dx, dx_lp, None, None
-    ws = torch.empty(nb, 2 * D, dtype=torch.float32, device=x.device)
-    dgamma = dbeta = None
-    if not defer:
-        dgamma = torch.empty(D, dtype=torch.float32, device=x.device)
-        dbeta = torch.empty(D, dtype=torch.float32, device=x.device)
-    call("evp_layernorm_bwd", ptr(_chk(dy)), dt(dy), ptr(x), ptr(x2), ptr(x3), ptr(gamma), ptr(mean), ptr(rstd),
-         ptr(gres), M, D, ptr(dx), ptr(dx_lp), ptr(dgamma), ptr(dbeta), ptr(ws), stream_ptr())
-    if defer:
-        _deferred.colsum(params[0], ws[:, :D])
-        _deferred.colsum(params[1], ws[:, D:])
     return dx, dx_lp, dgamma, dbeta
 
 
@@ -217,7 +226,6 @@ def set_window_mfma(flag):
     """A/B switch: Swin window attention on the MFMA kernels (default, bf16 mode) or on the f32 LDS kernels."""
     global _use_window_mfma
     _use_window_mfma = bool(flag)
-
 
 
 def set_fused_attention(flag):
@@ -654,7 +662,6 @@ def _bgrad(x2d, param=None):
     return colsum(x2d)
 
 
-
 # ----------------------------------------------------------------------------------------------------- stochastic regularisers
 class BlockDrop:
     """Stochastic regularisers of ONE call of a residual block (reference vit_block.py:241,252-253 / conv_block.py:35,43-49 /
@@ -724,14 +731,21 @@ def _branch_residual(a, w, bias, res, M, N, K, rd, which, rps, key):
     return y, mk
 
 
-def _branch_grad(g, rd, which, rps, mk, T):
-    """Gradient entering a branch whose output was added as res + drop_path(dropout(.)): (f32, compute-dtype copy)."""
-    bf = T == torch.bfloat16
-    gs, gs_lp = rows_scale(g, rd.u[which], rd.keep_prob, rps, want_lp=bf and mk is None)
+def _branch_grad(g, rd, which, rps, mk, T, side, lp=None):
+    """Gradient entering a residual branch whose output was added as res + drop_path(dropout(.)), g being the f32 gradient
+    of the sum: -> (f32 for the exact bias column sum, operand of the GEMMs in dtype T, column-sum partials | None).
+    `side`: g may carry the record of the LayerNorm backward that made it (_side_take); `lp`: its bf16 copy where the
+    caller holds one."""
+    side_lp, cs = _side_take(g) if side else (None, None)
+    if rd is None:
+        if lp is None:
+            lp = side_lp if side_lp is not None else cast(g, T)
+        return g, lp, cs
+    # the branch sees s_b * g (DropPath) times the dropout mask of its output
+    gs, gs_lp = rows_scale(g, rd.u[which], rd.keep_prob, rps, want_lp=T == torch.bfloat16 and mk is None)
     if mk is not None:
         gs = dropout_bwd(gs, mk, rd.drop)
-        gs_lp = cast(gs, T) if bf else None
-    return gs, (gs_lp if bf else gs)
+    return gs, (gs_lp if gs_lp is not None else cast(gs, T)), None
 
 
 # ----------------------------------------------------------------------------------------------------- autograd
@@ -798,12 +812,8 @@ class ViTBlockFn(torch.autograd.Function):
         g2 = _chk(g2.contiguous(), torch.float32).view(M, D)
         rd = ctx.rd
         mk_p, mk_h, mk_2 = ctx.drop_masks
-        # bf16 copy and column-sum partials of the incoming gradient, if the LayerNorm backward that made it left them
-        g2_side_lp, g2_cs = _side_take(g2) if bf else (None, None)
-        if rd is None:
-            g2b, g2_lp = g2, (g2_side_lp if g2_side_lp is not None else cast(g2, T))
-        else:                           # the MLP branch sees s_b * g (DropPath) times the fc2-output dropout mask
-            (g2b, g2_lp), g2_cs = _branch_grad(g2, rd, 1, N, mk_2, T), None
+        # with the bf16 copy and column-sum partials of the incoming gradient, if the LayerNorm backward that made it left them
+        g2b, g2_lp, g2_cs = _branch_grad(g2, rd, 1, N, mk_2, T, side=bf)
         qkvw_, qkvb_, pw_, pb_, f1w_, f1b_, f2w_, f2b_ = ctx.prm
         need = ctx.needs_input_grad
         # MLP
@@ -817,12 +827,7 @@ class ViTBlockFn(torch.autograd.Function):
         gemm(dh_pre, w1, dln2, M=M, N=D, K=Hd, trans_b=True, ldb=D)
         side = bf and rd is None
         g1, g1_lp, dn2w, dn2b = layernorm_bwd(dln2, x1, n2w, mean2, rstd2, gres=g2, want_lp=side, params=ctx.nprm[2:], side=side)
-        g1_side_lp, g1_cs = _side_take(g1) if side else (None, None)
-        g1b = g1
-        if rd is not None:
-            g1b, g1_lp = _branch_grad(g1, rd, 0, N, mk_p, T)
-        elif not bf:
-            g1_lp = g1
+        g1b, g1_lp, g1_cs = _branch_grad(g1, rd, 0, N, mk_p, T, side=side, lp=g1_lp)
         # attention
         dwp, dbp = _wgrad_bias(g1_lp, att, D, D, M, pw_, pb_, need[5], need[6], dy_f32=g1b, dy_colsum=g1_cs)
         datt = torch.empty(M, D, dtype=T, device=dev)
@@ -881,20 +886,10 @@ class PatchEmbedFn(torch.autograd.Function):
         dev = g.device
         g = _chk(g.contiguous(), torch.float32).view(M, D)
         dy = torch.empty(M, D, dtype=cols.dtype, device=dev)
-        nb = call("evp_layernorm_bwd_nblk", M)
-        ws = torch.empty(nb, 2 * D, dtype=torch.float32, device=dev)
-        # the per-block partials of d gamma / d beta join the step's grouped column-sum launch when the parameters can take deferred
-        # gradients (as layernorm_bwd does); otherwise the kernel's own finalize pass reduces them
-        defer = D % 8 == 0 and _deferred.can_defer(ctx.nprm[0]) and _deferred.can_defer(ctx.nprm[1])
-        dgamma = dbeta = None
-        if not defer:
-            dgamma = torch.empty(D, dtype=torch.float32, device=dev)
-            dbeta = torch.empty(D, dtype=torch.float32, device=dev)
+        ws, dgamma, dbeta, finish = _norm_grads(ctx.nprm, D, M, dev)
         call("evp_embed_post_bwd", ptr(g), ptr(y), ptr(gamma), ptr(beta), ptr(mean), ptr(rstd), M, D, ptr(dy), dt(dy),
              ptr(dgamma), ptr(dbeta), ptr(ws), stream_ptr())
-        if defer:
-            _deferred.colsum(ctx.nprm[0], ws[:, :D])
-            _deferred.colsum(ctx.nprm[1], ws[:, D:])
+        finish()
         dw = _wgrad(dy, cols, D, Kc, M, ctx.prm[0], ctx.wshape) if ctx.needs_input_grad[2] else None
         db = _bgrad(dy, ctx.prm[1]) if ctx.needs_input_grad[3] else None
         return None, None, dw, db, dgamma, dbeta, None, None
@@ -1324,10 +1319,7 @@ class PatchEmbedNHWCFn(torch.autograd.Function):
         dev = g.device
         g = _chk(g.contiguous(), torch.float32).view(M, D)
         dy = torch.empty(M, D, dtype=cols.dtype, device=dev)
-        dgamma = torch.empty(D, dtype=torch.float32, device=dev)
-        dbeta = torch.empty(D, dtype=torch.float32, device=dev)
-        nb = call("evp_layernorm_bwd_nblk", M)
-        ws = torch.empty(2 * nb * D, dtype=torch.float32, device=dev)
+        ws, dgamma, dbeta, _ = _norm_grads(None, D, M, dev)     # this form reduces d gamma / d beta in the kernel: nothing deferred
         call("evp_embed_post_bwd", ptr(g), ptr(y), ptr(gamma), ptr(beta), ptr(mean), ptr(rstd), M, D, ptr(dy), dt(dy), ptr(dgamma),
              ptr(dbeta), ptr(ws), stream_ptr())
         dw = _wgrad(dy, cols, D, Kc, M, ctx.prm[0], wshape) if ctx.needs_input_grad[2] else None
@@ -1450,14 +1442,10 @@ class ConvBlockFn(torch.autograd.Function):
         g2 = _chk(g2.contiguous(), torch.float32).view(M, Cc)
         # as in ViTBlockFn: bf16 copy / column sums left by the LayerNorm backward of the block above, bias gradients on the
         # weight-gradient launch, LayerNorm dgamma / dbeta through the grouped column sums
-        g2_side_lp, g2_cs = _side_take(g2) if bf else (None, None)
         rd = ctx.rd
         mk_h, mk_2 = ctx.drop_masks
         HW = H * W
-        if rd is None:
-            g2b, g2_lp = g2, (g2_side_lp if g2_side_lp is not None else cast(g2, T))
-        else:
-            (g2b, g2_lp), g2_cs = _branch_grad(g2, rd, 1, HW, mk_2, T), None
+        g2b, g2_lp, g2_cs = _branch_grad(g2, rd, 1, HW, mk_2, T, side=bf)
         dwf2, db2 = _wgrad_bias(g2_lp, h_act, Cc, Hd, M, f2w_, f2b_, need[13], need[14], dy_f32=g2b, shape=tuple(f2w_.shape), dy_colsum=g2_cs)
         dh_pre = torch.empty(M, Hd, dtype=T, device=dev)
         gemm(g2_lp, wf2, dh_pre, M=M, N=Hd, K=Cc, trans_b=True, ldb=Hd, act=ACT_DGELU, aux=h_pre)
@@ -1468,12 +1456,7 @@ class ConvBlockFn(torch.autograd.Function):
         gemm(dh_pre, wf1, dln2, M=M, N=Cc, K=Hd, trans_b=True, ldb=Cc)
         side = bf and rd is None
         g1, g1_lp, dn2w, dn2b = layernorm_bwd(dln2, x1, n2w, mean2, rstd2, gres=g2, want_lp=side, params=ctx.nprm[2:], side=side)
-        g1_side_lp, g1_cs = _side_take(g1) if side else (None, None)
-        g1b = g1
-        if rd is not None:
-            g1b, g1_lp = _branch_grad(g1, rd, 0, HW, None, T)
-        elif not bf:
-            g1_lp = g1
+        g1b, g1_lp, g1_cs = _branch_grad(g1, rd, 0, HW, None, T, side=side, lp=g1_lp)
         # conv branch
         dwc2, dbc2 = _wgrad_bias(g1_lp, a, Cc, Cc, M, c2w_, c2b_, need[7], need[8], dy_f32=g1b, shape=tuple(c2w_.shape), dy_colsum=g1_cs)
         da = torch.empty(M, Cc, dtype=T, device=dev)
@@ -1678,13 +1661,9 @@ class SwinBlockFn(torch.autograd.Function):
         g2 = _chk(g2.contiguous(), torch.float32).view(M, D)
         # as in ViTBlockFn: the LayerNorm backward that produced g2 (the block above, when no regrouping gather sits in between:
         # the single-group stages) may have left its bf16 copy and column sums; bias gradients ride on the weight-gradient launch
-        g2_side_lp, g2_cs = _side_take(g2) if bf else (None, None)
         rd = ctx.rd
         mk_p, mk_h, mk_2 = ctx.drop_masks
-        if rd is None:
-            g2b, g2_lp = g2, (g2_side_lp if g2_side_lp is not None else cast(g2, T))
-        else:
-            (g2b, g2_lp), g2_cs = _branch_grad(g2, rd, 1, N, mk_2, T), None
+        g2b, g2_lp, g2_cs = _branch_grad(g2, rd, 1, N, mk_2, T, side=bf)
         qkvw_, qkvb_, pw_, pb_, f1w_, f1b_, f2w_, f2b_ = ctx.prm
         need = ctx.needs_input_grad
         dw2, db2 = _wgrad_bias(g2_lp, h_act, D, Hd, M, f2w_, f2b_, need[13], need[14], dy_f32=g2b, dy_colsum=g2_cs)
@@ -1697,12 +1676,7 @@ class SwinBlockFn(torch.autograd.Function):
         gemm(dh_pre, w1, dln2, M=M, N=D, K=Hd, trans_b=True, ldb=D)
         side = bf and rd is None
         g1, g1_lp, dn2w, dn2b = layernorm_bwd(dln2, x1, n2w, mean2, rstd2, gres=g2, want_lp=side, params=ctx.nprm[2:], side=side)
-        g1_side_lp, g1_cs = _side_take(g1) if side else (None, None)
-        g1b = g1
-        if rd is not None:
-            g1b, g1_lp = _branch_grad(g1, rd, 0, N, mk_p, T)
-        elif not bf:
-            g1_lp = g1
+        g1b, g1_lp, g1_cs = _branch_grad(g1, rd, 0, N, mk_p, T, side=side, lp=g1_lp)
         dwp, dbp = _wgrad_bias(g1_lp, att, D, D, M, pw_, pb_, need[7], need[8], dy_f32=g1b, dy_colsum=g1_cs)
         datt = torch.empty(M, D, dtype=T, device=dev)
         gemm(g1_lp, wp, datt, M=M, N=D, K=D, trans_b=True, ldb=D)

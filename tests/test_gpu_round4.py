@@ -279,6 +279,82 @@ def test_swin_block_drop_path_and_dropout_match_oracle_for_given_draws(p_drop):
         assert torch.allclose(v.grad.cpu(), ref, atol=5e-5 * ref.abs().max().item() + 1e-6, rtol=3e-3), k
 
 
+@pytest.mark.parametrize("kind", ["vit", "swin"])
+def test_block_below_consumes_the_gradient_side_record(kind, monkeypatch):
+    """Two stacked blocks in bf16 mode: the last LayerNorm backward of the upper block records the bf16 copy and the column-sum
+    partials of its dx on the tensor, and the block below must USE them (a dead channel would give the same numbers, only slower).
+    Counted inside the lower block's backward: with the side data on, no cast of the incoming [M, D] gradient and the fc2 bias takes
+    the few partial rows; with it off, one cast and the full M-row column sum. Parameter gradients of both settings agree to the bound
+    test_gradient_path_switches_agree (test_gpu_round3.py) puts on the same comparison. D = 64 passes the D % 8 deferral gate and
+    takes the three-row LayerNorm backward."""
+    from eventpretrain_amd import ops
+    from eventpretrain_amd._lib import call
+    from eventpretrain_amd.model.sub_module.swin_block import SwinTransformerBlock
+    from eventpretrain_amd.model.sub_module.vit_block import ViTBlock
+    from eventpretrain_amd.testing import det_fill_module_
+    B, N, D, heads = 2, 8, 64, 2
+    M = B * N
+    g = torch.Generator().manual_seed(31)
+    if kind == "vit":
+        blocks = [ViTBlock(dim=D, num_heads=heads, mlp_ratio=4., qkv_bias=True) for _ in range(2)]
+        run = lambda blk, t: blk(t)
+    else:
+        blocks = [SwinTransformerBlock(dim=D, input_resolution=(14, 14), num_heads=heads, window_size=7, shift_size=0, mlp_ratio=4.)
+                  for _ in range(2)]
+        rel = torch.randint(0, 169, (1, N, N), generator=g).to(torch.int32).cuda()          # one group
+        run = lambda blk, t: blk(t, rel)
+    for blk in blocks:
+        det_fill_module_(blk)
+        blk.cuda().train()
+    lower, upper = blocks
+    x = torch.randn(B, N, D, generator=g).cuda()
+    w = torch.randn(B, N, D, generator=g).cuda()
+    ops.set_compute_dtype(torch.bfloat16)
+    in_lower, casts, fc2_rows = [], [], []
+    real_cast, real_colsum = ops.cast, ops._deferred.colsum
+
+    def cast(t, dtype):
+        if in_lower and t.dtype == torch.float32 and dtype == torch.bfloat16:
+            casts.append(tuple(t.shape))
+        return real_cast(t, dtype)
+
+    def colsum(param, x2d):
+        if param is lower.mlp.fc2.bias:
+            fc2_rows.append(x2d.shape[0])
+        return real_colsum(param, x2d)
+
+    monkeypatch.setattr(ops, "cast", cast)
+    monkeypatch.setattr(ops._deferred, "colsum", colsum)
+
+    def grads(flag):
+        ops.set_grad_side(flag)
+        del in_lower[:], casts[:], fc2_rows[:]
+        for blk in blocks:
+            for p in blk.parameters():
+                p.grad = None
+        xt = x.clone().requires_grad_(True)
+        h = run(lower, xt)
+        h.register_hook(lambda _: in_lower.append(True))           # fires when the upper block has handed its gradient down
+        (run(upper, h) * w).sum().backward()
+        ops.flush_deferred_grads()
+        torch.cuda.synchronize()
+        got = {f"{i}.{k}": p.grad.clone() for i, blk in enumerate(blocks) for k, p in blk.named_parameters() if p.grad is not None}
+        got["x"] = xt.grad.clone()
+        return got, list(casts), list(fc2_rows)
+
+    on, casts_on, rows_on = grads(True)
+    off, casts_off, rows_off = grads(False)
+    nblk = call("evp_layernorm_bwd_nblk", M)
+    assert nblk < M
+    assert casts_on == [] and rows_on == [nblk], (casts_on, rows_on)
+    assert casts_off == [(M, D)] and rows_off == [M], (casts_off, rows_off)
+    assert on.keys() == off.keys() and len(on) == 1 + sum(1 for blk in blocks for p in blk.parameters() if p.requires_grad)
+    for k in off:
+        ref = off[k].float()
+        err = (on[k].float() - ref).abs().max().item()
+        assert torch.isfinite(on[k]).all() and err <= 2e-2 * ref.abs().max().item() + 1e-7, (k, err, ref.abs().max().item())
+
+
 def test_finetune_epoch_runs_captured_and_follows_the_eager_loop():
     """ft_train_one_epoch builds its own step executor (auto_ft_step_executor). (a) Regularisers off, f32: the
     captured epoch's losses and final weights equal the eager loop's (args.graph_step = False) from the same start. (b) The recipe's
