@@ -227,7 +227,7 @@ __device__ __forceinline__ float frag_f32(const char *img, int rb, int ks, int l
 
 // ragged right edge (N not a multiple of 4, e.g. attention scores with N = 98): element-wise and out of line. All
 // arguments by value: taking the address of the kernel-argument struct would push it (and every pointer derived from
-// it) into scratch memory.
+// it) into scratch memory. Keeps its own arithmetic on purpose: scalar gelu_sel / dgelu_sel, not the packed polynomial of epi_act4.
 template <typename TC>
 __device__ __noinline__ void epilogue_edge(TC *C, TC *aux, const float *bias, const float *residual, float alpha, int act,
                                            int accumulate, int splitk, int64_t o, int64_t ao, int64_t ro, int n, int nv,
@@ -249,9 +249,7 @@ __device__ __noinline__ void epilogue_edge(TC *C, TC *aux, const float *bias, co
   }
 }
 
-// EPI: 0 = linear (bias / residual / accumulate), 1 = activation forward (GELU / ReLU, optional pre-activation store),
-//      2 = activation backward (multiply by act'(aux))
-// One 4-wide piece C[m][n..n+3] of the epilogue; `a` = raw accumulators.
+// One 4-wide piece C[m][n..n+3] of the epilogue; `a` = raw accumulators. (EPI and the arithmetic: gemm_common.h, epi_pre4 / epi_act4.)
 template <typename TC, int EPI>
 __device__ __forceinline__ void epi_apply4(float4 a, const GemmParams &p, int64_t coff, int m, int n, float4 bias4, bool fast) {
   TC *C = reinterpret_cast<TC *>(p.C);
@@ -261,32 +259,44 @@ __device__ __forceinline__ void epi_apply4(float4 a, const GemmParams &p, int64_
                       p.N - n, a.x, a.y, a.z, fast);
     return;
   }
-  float4 v = make_float4(a.x * p.alpha + bias4.x, a.y * p.alpha + bias4.y, a.z * p.alpha + bias4.z, a.w * p.alpha + bias4.w);
+  float4 v = epi_pre4(a, p.alpha, bias4), h = make_float4(0.f, 0.f, 0.f, 0.f);
   const int64_t ao = coff + (int64_t)m * p.ldaux + n;
-  if constexpr (EPI == 1) {
-    if (p.aux) st4<TC>(reinterpret_cast<TC *>(p.aux) + ao, v);
-    if (p.act == EVP_ACT_GELU) v = gelu4(v, fast);
-    else v = make_float4(fmaxf(v.x, 0.f), fmaxf(v.y, 0.f), fmaxf(v.z, 0.f), fmaxf(v.w, 0.f));
-  } else if constexpr (EPI == 2) {
-    const float4 h = ld4<TC>(reinterpret_cast<const TC *>(p.aux) + ao);
-    if (p.act == EVP_ACT_DGELU) v = dgelu_mul4(v, h, fast);
-    else v = make_float4(h.x > 0.f ? v.x : 0.f, h.y > 0.f ? v.y : 0.f, h.z > 0.f ? v.z : 0.f, h.w > 0.f ? v.w : 0.f);
-  }
-  if (p.residual) {
-    const float4 r = *reinterpret_cast<const float4 *>(p.residual + coff + (int64_t)m * p.ldres + n);
-    v = make_float4(v.x + r.x, v.y + r.y, v.z + r.z, v.w + r.w);
-  }
+  if constexpr (EPI == 1) { if (p.aux) st4<TC>(reinterpret_cast<TC *>(p.aux) + ao, v); }
+  if constexpr (EPI == 2) h = ld4<TC>(reinterpret_cast<const TC *>(p.aux) + ao);
+  v = epi_act4<EPI>(v, h, p.act, fast);
+  if (p.residual) v = add4(v, *reinterpret_cast<const float4 *>(p.residual + coff + (int64_t)m * p.ldres + n));
   const int64_t o = coff + (int64_t)m * p.ldc + n;
   if (p.splitk > 1) {          // split-K partial sums meet in HBM (f32 C, zeroed by the launcher)
     float *c = reinterpret_cast<float *>(p.C) + o;
     atomicAdd(c + 0, v.x); atomicAdd(c + 1, v.y); atomicAdd(c + 2, v.z); atomicAdd(c + 3, v.w);
     return;
   }
-  if (p.accumulate) {
-    const float4 c = ld4<TC>(C + o);
-    v = make_float4(v.x + c.x, v.y + c.y, v.z + c.z, v.w + c.w);
-  }
+  if (p.accumulate) v = add4(v, ld4<TC>(C + o));
   st4<TC>(C + o, v);
+}
+
+// Which optional operands an interior (branch-free) form handles: calls f(RES, ACC, AUXST) with std::bool_constant arguments for
+// residual present / accumulate into C / store the pre-activation, and returns true. AUXST follows p.aux and exists for the
+// activation forward only. Accumulate has branch-free forms for f32 C without an activation forward: evp_gemm refuses it with a
+// bf16 C, and with GELU / ReLU no caller builds it -- false then, and the caller takes the generic pieces (epi_apply4).
+template <typename TC, int EPI, typename F> __device__ __forceinline__ bool epi_flags(const GemmParams &p, F f) {
+  constexpr bool CAN_ACC = sizeof(TC) == 4 && EPI != 1;
+  if (!CAN_ACC && p.accumulate) return false;
+  auto on_aux = [&](auto res, auto acc) {
+    if constexpr (EPI == 1) {
+      if (p.aux) return f(res, acc, std::true_type{});
+    }
+    f(res, acc, std::false_type{});
+  };
+  auto on_acc = [&](auto res) {
+    if constexpr (CAN_ACC) {
+      if (p.accumulate) return on_aux(res, std::true_type{});
+    }
+    on_aux(res, std::false_type{});
+  };
+  if (p.residual) on_acc(std::true_type{});
+  else on_acc(std::false_type{});
+  return true;
 }
 
 // Interior fast path of the epilogue for one row of NI 4-wide pieces (n = n0 + 16 j): the optional operands are
@@ -296,7 +306,7 @@ __device__ __forceinline__ void epi_apply4(float4 a, const GemmParams &p, int64_
 template <typename TC, int EPI, int NI, bool RES, bool ACC, bool AUXST>
 __device__ __forceinline__ void epi_row_fast(const float4 (&a)[NI], const GemmParams &p, const float4 (&bias4)[NI], TC *crow, TC *auxrow,
                                              const float *resrow, bool fast) {
-  float4 h[NI], r[NI], c[NI];
+  float4 h[NI] = {}, r[NI], c[NI];
 #pragma unroll
   for (int j = 0; j < NI; ++j) {
     if constexpr (EPI == 2) h[j] = ld4<TC>(auxrow + j * 16);
@@ -305,18 +315,11 @@ __device__ __forceinline__ void epi_row_fast(const float4 (&a)[NI], const GemmPa
   }
 #pragma unroll
   for (int j = 0; j < NI; ++j) {
-    float4 v = make_float4(a[j].x * p.alpha + bias4[j].x, a[j].y * p.alpha + bias4[j].y, a[j].z * p.alpha + bias4[j].z,
-                           a[j].w * p.alpha + bias4[j].w);
-    if constexpr (EPI == 1) {
-      if constexpr (AUXST) st4<TC>(auxrow + j * 16, v);
-      if (p.act == EVP_ACT_GELU) v = gelu4(v, fast);
-      else v = make_float4(fmaxf(v.x, 0.f), fmaxf(v.y, 0.f), fmaxf(v.z, 0.f), fmaxf(v.w, 0.f));
-    } else if constexpr (EPI == 2) {
-      if (p.act == EVP_ACT_DGELU) v = dgelu_mul4(v, h[j], fast);
-      else v = make_float4(h[j].x > 0.f ? v.x : 0.f, h[j].y > 0.f ? v.y : 0.f, h[j].z > 0.f ? v.z : 0.f, h[j].w > 0.f ? v.w : 0.f);
-    }
-    if constexpr (RES) v = make_float4(v.x + r[j].x, v.y + r[j].y, v.z + r[j].z, v.w + r[j].w);
-    if constexpr (ACC) v = make_float4(v.x + c[j].x, v.y + c[j].y, v.z + c[j].z, v.w + c[j].w);
+    float4 v = epi_pre4(a[j], p.alpha, bias4[j]);
+    if constexpr (AUXST) st4<TC>(auxrow + j * 16, v);
+    v = epi_act4<EPI>(v, h[j], p.act, fast);
+    if constexpr (RES) v = add4(v, r[j]);
+    if constexpr (ACC) v = add4(v, c[j]);
     st4<TC>(crow + j * 16, v);
   }
 }
@@ -348,19 +351,11 @@ template <typename TC, int EPI, int MI, int NI>
 __device__ __forceinline__ void epilogue(const f32x4 (&acc)[MI][NI], const GemmParams &p, int64_t coff, int mbase, int nbase, bool fast) {
   if (p.dbg == 1 && acc[0][0][0] != 12345.678f) return;
   const bool interior = mbase + (MI - 1) * 16 < p.M && nbase + (NI - 1) * 16 + 3 < p.N && p.splitk <= 1;
-  if (interior) {
-    const bool res = p.residual != nullptr, accu = p.accumulate != 0, auxst = p.aux != nullptr;
-    if (res) {
-      if (accu) epilogue_fast<TC, EPI, MI, NI, true, true, true>(acc, p, coff, mbase, nbase, fast);      // rare: keep one generic-ish form
-      else if (auxst || EPI != 1) epilogue_fast<TC, EPI, MI, NI, true, false, true>(acc, p, coff, mbase, nbase, fast);
-      else epilogue_fast<TC, EPI, MI, NI, true, false, false>(acc, p, coff, mbase, nbase, fast);
-    } else {
-      if (accu) epilogue_fast<TC, EPI, MI, NI, false, true, true>(acc, p, coff, mbase, nbase, fast);
-      else if (auxst || EPI != 1) epilogue_fast<TC, EPI, MI, NI, false, false, true>(acc, p, coff, mbase, nbase, fast);
-      else epilogue_fast<TC, EPI, MI, NI, false, false, false>(acc, p, coff, mbase, nbase, fast);
-    }
+  if (interior && epi_flags<TC, EPI>(p, [&](auto res, auto accu, auto auxst) {
+        constexpr bool RES = decltype(res)::value, ACC = decltype(accu)::value, AUXST = decltype(auxst)::value;
+        epilogue_fast<TC, EPI, MI, NI, RES, ACC, AUXST>(acc, p, coff, mbase, nbase, fast);
+      }))
     return;
-  }
   float4 bias4[NI];
 #pragma unroll
   for (int j = 0; j < NI; ++j) {
@@ -408,7 +403,7 @@ __device__ __forceinline__ void epilogue_lds_rows(const float4 *tile, const Gemm
   const float *res = p.residual + coff + n;
 #pragma unroll 1
   for (int s = 0; s < STEPS; s += 4) {
-    float4 a[4], h[4], r[4], c[4];
+    float4 a[4], h[4] = {}, r[4], c[4];
     int m[4];
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
@@ -421,17 +416,11 @@ __device__ __forceinline__ void epilogue_lds_rows(const float4 *tile, const Gemm
     }
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
-      float4 v = make_float4(a[u].x * p.alpha + bias4.x, a[u].y * p.alpha + bias4.y, a[u].z * p.alpha + bias4.z, a[u].w * p.alpha + bias4.w);
-      if constexpr (EPI == 1) {
-        if constexpr (AUXST) st4<TC>(aux + (int64_t)m[u] * p.ldaux, v);
-        if (p.act == EVP_ACT_GELU) v = gelu4(v, fast);
-        else v = make_float4(fmaxf(v.x, 0.f), fmaxf(v.y, 0.f), fmaxf(v.z, 0.f), fmaxf(v.w, 0.f));
-      } else if constexpr (EPI == 2) {
-        if (p.act == EVP_ACT_DGELU) v = dgelu_mul4(v, h[u], fast);
-        else v = make_float4(h[u].x > 0.f ? v.x : 0.f, h[u].y > 0.f ? v.y : 0.f, h[u].z > 0.f ? v.z : 0.f, h[u].w > 0.f ? v.w : 0.f);
-      }
-      if constexpr (RES) v = make_float4(v.x + r[u].x, v.y + r[u].y, v.z + r[u].z, v.w + r[u].w);
-      if constexpr (ACC) v = make_float4(v.x + c[u].x, v.y + c[u].y, v.z + c[u].z, v.w + c[u].w);
+      float4 v = epi_pre4(a[u], p.alpha, bias4);
+      if constexpr (AUXST) st4<TC>(aux + (int64_t)m[u] * p.ldaux, v);
+      v = epi_act4<EPI>(v, h[u], p.act, fast);
+      if constexpr (RES) v = add4(v, r[u]);
+      if constexpr (ACC) v = add4(v, c[u]);
       st4<TC>(C + (int64_t)m[u] * p.ldc, v);
     }
   }
@@ -453,7 +442,7 @@ __device__ __forceinline__ void epilogue_lds_rows8(const float4 *tile, const Gem
 #pragma unroll 1
   for (int s = 0; s < STEPS; s += G) {
     float4 a0[G], a1[G];
-    uint4 h[G];
+    uint4 h[G] = {};
     int m[G];
 #pragma unroll
     for (int u = 0; u < G; ++u) {
@@ -465,26 +454,14 @@ __device__ __forceinline__ void epilogue_lds_rows8(const float4 *tile, const Gem
     }
 #pragma unroll
     for (int u = 0; u < G; ++u) {
-      float4 v0 = make_float4(a0[u].x * p.alpha + b0.x, a0[u].y * p.alpha + b0.y, a0[u].z * p.alpha + b0.z, a0[u].w * p.alpha + b0.w);
-      float4 v1 = make_float4(a1[u].x * p.alpha + b1.x, a1[u].y * p.alpha + b1.y, a1[u].z * p.alpha + b1.z, a1[u].w * p.alpha + b1.w);
-      if constexpr (EPI == 1) {
-        if constexpr (AUXST) st8_bf16_wt(Ab, coff + (int64_t)m[u] * p.ldaux + n, v0, v1);
-        if (p.act == EVP_ACT_GELU) { v0 = gelu4(v0, fast); v1 = gelu4(v1, fast); }
-        else {
-          v0 = make_float4(fmaxf(v0.x, 0.f), fmaxf(v0.y, 0.f), fmaxf(v0.z, 0.f), fmaxf(v0.w, 0.f));
-          v1 = make_float4(fmaxf(v1.x, 0.f), fmaxf(v1.y, 0.f), fmaxf(v1.z, 0.f), fmaxf(v1.w, 0.f));
-        }
-      } else if constexpr (EPI == 2) {
-        const float4 h0 = make_float4(__uint_as_float(h[u].x << 16), __uint_as_float(h[u].x & 0xFFFF0000u), __uint_as_float(h[u].y << 16),
-                                      __uint_as_float(h[u].y & 0xFFFF0000u));
-        const float4 h1 = make_float4(__uint_as_float(h[u].z << 16), __uint_as_float(h[u].z & 0xFFFF0000u), __uint_as_float(h[u].w << 16),
-                                      __uint_as_float(h[u].w & 0xFFFF0000u));
-        if (p.act == EVP_ACT_DGELU) { v0 = dgelu_mul4(v0, h0, fast); v1 = dgelu_mul4(v1, h1, fast); }
-        else {
-          v0 = make_float4(h0.x > 0.f ? v0.x : 0.f, h0.y > 0.f ? v0.y : 0.f, h0.z > 0.f ? v0.z : 0.f, h0.w > 0.f ? v0.w : 0.f);
-          v1 = make_float4(h1.x > 0.f ? v1.x : 0.f, h1.y > 0.f ? v1.y : 0.f, h1.z > 0.f ? v1.z : 0.f, h1.w > 0.f ? v1.w : 0.f);
-        }
-      }
+      float4 v0 = epi_pre4(a0[u], p.alpha, b0), v1 = epi_pre4(a1[u], p.alpha, b1);
+      if constexpr (AUXST) st8_bf16_wt(Ab, coff + (int64_t)m[u] * p.ldaux + n, v0, v1);
+      const float4 h0 = unpack_bf16x4(make_uint2(h[u].x, h[u].y)), h1 = unpack_bf16x4(make_uint2(h[u].z, h[u].w));
+      // one test of p.act for both pieces (inside each arm epi_act4's own test folds away): tested per piece, the two polynomial chains
+      // land in separate blocks and no longer interleave (profiles/gemm_epilogue_refactor.txt, section 6)
+      constexpr int SMOOTH = EPI == 2 ? EVP_ACT_DGELU : EVP_ACT_GELU, STEP = EPI == 2 ? EVP_ACT_DRELU : EVP_ACT_RELU;
+      if (p.act == SMOOTH) { v0 = epi_act4<EPI>(v0, h0, SMOOTH, fast); v1 = epi_act4<EPI>(v1, h1, SMOOTH, fast); }
+      else { v0 = epi_act4<EPI>(v0, h0, STEP, fast); v1 = epi_act4<EPI>(v1, h1, STEP, fast); }
       st8_bf16_wt(Cb, coff + (int64_t)m[u] * p.ldc + n, v0, v1);
     }
   }
@@ -519,19 +496,12 @@ __device__ __forceinline__ void epilogue_lds(const f32x4 (&acc)[MI][NI], const G
   if (n >= p.N) return;
   const float4 bias4 = (p.bias && n + 3 < p.N) ? *reinterpret_cast<const float4 *>(p.bias + n) : make_float4(0.f, 0.f, 0.f, 0.f);
   constexpr int RPP = NT / CPR;                    // rows per pass
-  if (m0 + BM <= p.M && n + 3 < p.N && p.splitk <= 1) {      // interior: branch-free, loads batched four rows at a time
-    const bool res = p.residual != nullptr, accu = p.accumulate != 0, auxst = p.aux != nullptr;
-    if (res) {
-      if (accu) epilogue_lds_rows<TC, EPI, BM, BN, NT, true, true, true>(tile, p, coff, m0, n, ch, r0, bias4, fast);
-      else if (auxst || EPI != 1) epilogue_lds_rows<TC, EPI, BM, BN, NT, true, false, true>(tile, p, coff, m0, n, ch, r0, bias4, fast);
-      else epilogue_lds_rows<TC, EPI, BM, BN, NT, true, false, false>(tile, p, coff, m0, n, ch, r0, bias4, fast);
-    } else {
-      if (accu) epilogue_lds_rows<TC, EPI, BM, BN, NT, false, true, true>(tile, p, coff, m0, n, ch, r0, bias4, fast);
-      else if (auxst || EPI != 1) epilogue_lds_rows<TC, EPI, BM, BN, NT, false, false, true>(tile, p, coff, m0, n, ch, r0, bias4, fast);
-      else epilogue_lds_rows<TC, EPI, BM, BN, NT, false, false, false>(tile, p, coff, m0, n, ch, r0, bias4, fast);
-    }
+  const bool interior = m0 + BM <= p.M && n + 3 < p.N && p.splitk <= 1;      // branch-free, loads batched four rows at a time
+  if (interior && epi_flags<TC, EPI>(p, [&](auto res, auto accu, auto auxst) {
+        constexpr bool RES = decltype(res)::value, ACC = decltype(accu)::value, AUXST = decltype(auxst)::value;
+        epilogue_lds_rows<TC, EPI, BM, BN, NT, RES, ACC, AUXST>(tile, p, coff, m0, n, ch, r0, bias4, fast);
+      }))
     return;
-  }
   for (int r = r0; r < BM; r += RPP) {
     const int m = m0 + r;
     if (m >= p.M) break;
@@ -798,14 +768,13 @@ int launch(const evp_gemm_desc *d, hipStream_t s) {
   p.residual = d->residual; p.ldres = d->ldres; p.accumulate = d->accumulate; p.dbg = g_gemm_dbg; p.colsum = nullptr; p.colsum_acc = 0; p.stamp = evp_gemm_next_stamp_slot();
   p.tiles_m = (d->M + BM - 1) / BM;
   const int tiles_n = (d->N + BN - 1) / BN;
+  const int nb = (d->batch0 > 0 ? d->batch0 : 1) * p.batch1;
   {
     // the 8-column epilogue form: bf16 C (and aux) in one piece below 2 GiB, rows and bases 16-byte aligned
-    const int nbz = (d->batch0 > 0 ? d->batch0 : 1) * (d->batch1 > 0 ? d->batch1 : 1);
     const int64_t span = (int64_t)d->M * (d->ldc > d->ldaux ? d->ldc : d->ldaux) * 2;
-    p.c_wt16 = (g_gemm_wt16 && d->c_dtype == EVP_BF16 && nbz == 1 && span < 0x7FFFFFFFLL && d->ldc % 8 == 0 && (!d->aux || d->ldaux % 8 == 0) &&
+    p.c_wt16 = (g_gemm_wt16 && d->c_dtype == EVP_BF16 && nb == 1 && span < 0x7FFFFFFFLL && d->ldc % 8 == 0 && (!d->aux || d->ldaux % 8 == 0) &&
                 ((uintptr_t)d->C & 15) == 0 && ((uintptr_t)d->aux & 15) == 0 && (!d->bias || ((uintptr_t)d->bias & 15) == 0)) ? 1 : 0;
   }
-  const int nb = (d->batch0 > 0 ? d->batch0 : 1) * p.batch1;
   // split-K: only for plain f32 outputs without epilogue extras (the weight-gradient GEMMs: few output tiles, long K)
   constexpr int BKc = BK;
   int splitk = d->splitk;

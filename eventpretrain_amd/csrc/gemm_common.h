@@ -120,13 +120,34 @@ __device__ __forceinline__ float4 dgelu_mul4(float4 v, float4 h, bool fast) {   
   return make_float4(v.x * dgelu_sel(h.x, false), v.y * dgelu_sel(h.y, false), v.z * dgelu_sel(h.z, false), v.w * dgelu_sel(h.w, false));
 }
 
-template <typename TC> __device__ __forceinline__ float4 ld4(const TC *p);
-template <> __device__ __forceinline__ float4 ld4<float>(const float *p) { return *reinterpret_cast<const float4 *>(p); }
-template <> __device__ __forceinline__ float4 ld4<bf16_t>(const bf16_t *p) {
-  const uint2 u = *reinterpret_cast<const uint2 *>(p);
+// ---- the epilogue arithmetic of one 4-wide piece, written once for every form of gemm.hip and gemm_g4_body.h ---------------------
+// Order (the library is built with -ffp-contract=off, so the order is the result, bit for bit): pre = acc * alpha + bias [stored as the
+// pre-activation where the caller wants it], then the activation, then + residual, then + C. The forms differ only in how they load
+// and store around these three functions.
+// EPI: 0 = linear (bias / residual / accumulate), 1 = activation forward (GELU / ReLU, optional pre-activation store),
+//      2 = activation backward (multiply by act'(h), h = the stored pre-activation)
+__device__ __forceinline__ float4 add4(float4 a, float4 b) { return make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w); }
+__device__ __forceinline__ float4 epi_pre4(float4 acc, float alpha, float4 bias4) {
+  return make_float4(acc.x * alpha + bias4.x, acc.y * alpha + bias4.y, acc.z * alpha + bias4.z, acc.w * alpha + bias4.w);
+}
+template <int EPI> __device__ __forceinline__ float4 epi_act4(float4 v, float4 h, int act, bool fast) {
+  if constexpr (EPI == 1) {
+    if (act == EVP_ACT_GELU) return gelu4(v, fast);
+    return make_float4(fmaxf(v.x, 0.f), fmaxf(v.y, 0.f), fmaxf(v.z, 0.f), fmaxf(v.w, 0.f));
+  } else if constexpr (EPI == 2) {
+    if (act == EVP_ACT_DGELU) return dgelu_mul4(v, h, fast);
+    return make_float4(h.x > 0.f ? v.x : 0.f, h.y > 0.f ? v.y : 0.f, h.z > 0.f ? v.z : 0.f, h.w > 0.f ? v.w : 0.f);
+  }
+  return v;
+}
+
+__device__ __forceinline__ float4 unpack_bf16x4(uint2 u) {
   return make_float4(__uint_as_float(u.x << 16), __uint_as_float(u.x & 0xFFFF0000u), __uint_as_float(u.y << 16),
                      __uint_as_float(u.y & 0xFFFF0000u));
 }
+template <typename TC> __device__ __forceinline__ float4 ld4(const TC *p);
+template <> __device__ __forceinline__ float4 ld4<float>(const float *p) { return *reinterpret_cast<const float4 *>(p); }
+template <> __device__ __forceinline__ float4 ld4<bf16_t>(const bf16_t *p) { return unpack_bf16x4(*reinterpret_cast<const uint2 *>(p)); }
 template <typename TC> __device__ __forceinline__ void st4(TC *p, float4 v);
 // Write-through stores (agent-scope relaxed atomic store = `global_store ... sc1`) for 8-byte-per-lane output pieces. A kernel's plain
 // stores stay dirty in the eight XCDs' L2s until the end-of-kernel release writes them back (MI355X_MICROARCH.md price list: a kernel

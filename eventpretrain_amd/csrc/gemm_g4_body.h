@@ -359,7 +359,6 @@ template <bool KC, int F> struct G4Operand {
 // runs on the f32 accumulators in registers, the rounded bf16 tile is parked in the (now idle) ring -- row-major, 16-byte chunk
 // index XORed with (row & 15) -- and every thread then walks rows with a FIXED chunk column: each wave store instruction covers
 // 2-4 whole contiguous rows of the tile. The GELU' operand (pre-activation) comes in the same way: rows -> LDS -> lane pieces.
-struct G4Piece { float x, y, z, w; };
 __device__ __forceinline__ uint2 pack_bf16x4(float a, float b, float c, float d) {
   uint2 u;
   u.x = (uint32_t)f32_to_bf16(a) | ((uint32_t)f32_to_bf16(b) << 16);
@@ -459,19 +458,11 @@ __device__ __forceinline__ void g4x_epilogue_bf16(const f32x16 (&acc)[FI][FJ], c
           const float4 b4 = bias4[jj][g];
 #pragma unroll
           for (int i = 0; i < FI; ++i) {
-            float4 v = make_float4(acc[i][j][4 * g] * p.alpha + b4.x, acc[i][j][4 * g + 1] * p.alpha + b4.y, acc[i][j][4 * g + 2] * p.alpha + b4.z,
-                                   acc[i][j][4 * g + 3] * p.alpha + b4.w);
             uint2 *dst = piece_ptr(i, j, g);
-            if constexpr (MODE == 1) {
-              if (p.act == EVP_ACT_GELU) v = gelu4(v, true);
-              else v = make_float4(fmaxf(v.x, 0.f), fmaxf(v.y, 0.f), fmaxf(v.z, 0.f), fmaxf(v.w, 0.f));
-            } else if constexpr (MODE == 2) {
-              const uint2 hu = *dst;
-              const float4 h = make_float4(__uint_as_float(hu.x << 16), __uint_as_float(hu.x & 0xFFFF0000u), __uint_as_float(hu.y << 16),
-                                           __uint_as_float(hu.y & 0xFFFF0000u));
-              if (p.act == EVP_ACT_DGELU) v = dgelu_mul4(v, h, true);
-              else v = make_float4(h.x > 0.f ? v.x : 0.f, h.y > 0.f ? v.y : 0.f, h.z > 0.f ? v.z : 0.f, h.w > 0.f ? v.w : 0.f);
-            }
+            float4 h = make_float4(0.f, 0.f, 0.f, 0.f);
+            if constexpr (MODE == 2) h = unpack_bf16x4(*dst);
+            const float4 a = make_float4(acc[i][j][4 * g], acc[i][j][4 * g + 1], acc[i][j][4 * g + 2], acc[i][j][4 * g + 3]);
+            const float4 v = epi_act4<MODE>(epi_pre4(a, p.alpha, b4), h, p.act, true);
             *dst = pack_bf16x4(v.x, v.y, v.z, v.w);
           }
         }
@@ -525,9 +516,8 @@ __device__ __forceinline__ void g4x_epilogue_f32(const f32x16 (&acc)[FI][FJ], co
       for (int i = 0; i < FI; ++i) {
         const int m = mrow + 32 * i;
         if (m >= p.M) continue;
-        const float4 v = make_float4(acc[i][j][4 * g] * p.alpha + b4.x + r[i].x + c[i].x, acc[i][j][4 * g + 1] * p.alpha + b4.y + r[i].y + c[i].y,
-                                     acc[i][j][4 * g + 2] * p.alpha + b4.z + r[i].z + c[i].z, acc[i][j][4 * g + 3] * p.alpha + b4.w + r[i].w + c[i].w);
-        *reinterpret_cast<float4 *>(C + (int64_t)m * p.ldc + n) = v;
+        const float4 a = make_float4(acc[i][j][4 * g], acc[i][j][4 * g + 1], acc[i][j][4 * g + 2], acc[i][j][4 * g + 3]);
+        *reinterpret_cast<float4 *>(C + (int64_t)m * p.ldc + n) = add4(add4(epi_pre4(a, p.alpha, b4), r[i]), c[i]);
       }
     }
 }

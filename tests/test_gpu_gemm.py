@@ -402,3 +402,40 @@ def test_eight_column_write_through_epilogue_is_bit_identical_and_falls_back():
         h2 = torch.empty(M, N, dtype=torch.bfloat16, device="cuda")
         ops.gemm(a, b, h2, M=M, N=N, K=K, bias=bias, act=ACT_GELU, aux=aux_off)
         assert torch.equal(h2, new[1]) and torch.equal(aux_off, new[2])
+
+
+def test_epilogue_forms_agree_bitwise():
+    """One epilogue arithmetic for every form (gemm_common.h epi_pre4 / epi_act4): the same problem under the 128x128, 64x64 and
+    96x128 tilings gives the same bits -- the k order per element is the same in all of them, and rows 128-191 of the 200x136 output are
+    interior under the 64-row tiling and ragged under the 128-row one, so the register, 4-column, 8-column and generic forms all meet
+    here. Each result also against float64 (1e-4 for f32, 2e-2 for bf16, relative to |ref| + 1). The cases are those of
+    tools/gemm_epilogue_digest.py plus GELU + accumulate without a pre-activation buffer, where the interior forms used to store the
+    pre-activation through the null aux pointer."""
+    from eventpretrain_amd._lib import ACT_DGELU, ACT_DRELU, ACT_GELU, ACT_RELU
+    from tools.gemm_epilogue_digest import ALPHA, CASES, Case, admits, problem, run
+    M, N, K = 200, 136, 96
+    cases = CASES + [Case("gelu+acc, no aux", ACT_GELU, True, False, True, False)]
+    for dtype, tiles, tol in ((torch.bfloat16, (1, 2, 4), 2e-2), (torch.float32, (1, 2), 1e-4)):
+        p = problem(M, N, K, N, dtype, seed=9)
+        base = ALPHA * (p["a"].cpu().double() @ p["b"].cpu().double().t())
+        for c_dtype in (torch.float32, torch.bfloat16):
+            h = p["h"].to(c_dtype).cpu().double()          # the pre-activation an activation backward reads, as stored
+            cdf = 0.5 * (1.0 + torch.erf(h / math.sqrt(2.0)))
+            for case in cases:
+                if not admits(case, dtype, c_dtype, tiles[0]):
+                    continue
+                pre = base + (p["bias"].cpu().double() if case.bias else 0.0)
+                ref = {ACT_GELU: torch.nn.functional.gelu(pre), ACT_RELU: torch.relu(pre), ACT_DRELU: pre * (h > 0).double(),
+                       ACT_DGELU: pre * (cdf + h * torch.exp(-0.5 * h * h) / math.sqrt(2.0 * math.pi))}.get(case.act, pre)
+                if case.residual:
+                    ref = ref + p["res"].cpu().double()
+                if case.accumulate:
+                    ref = ref + p["c0"].cpu().double()
+                outs = [run(case, p, c_dtype, t) for t in tiles]
+                for t, (c, aux) in zip(tiles, outs):
+                    assert torch.equal(c, outs[0][0]), (case.name, dtype, c_dtype, t)
+                    assert ((c.cpu().double() - ref).abs() / (ref.abs() + 1.0)).max().item() <= tol, (case.name, dtype, c_dtype, t)
+                    assert (aux is None) == (outs[0][1] is None)
+                    if aux is not None:
+                        assert torch.equal(aux, outs[0][1]), (case.name, dtype, c_dtype, t, "aux")
+                        assert ((aux.cpu().double() - pre).abs() / (pre.abs() + 1.0)).max().item() <= tol, (case.name, dtype, c_dtype, t, "aux")
