@@ -15,8 +15,9 @@ stage the optimizer's per-step scalars (lr, bias corrections) into the pinned ta
 replay. Collectives stay outside the graphs. If capture fails the executor says so and keeps stepping eagerly.
 
 Replaces nothing in the reference (its loop is eager PyTorch, trainer/pretrain/pr_trainer.py:20-76); it is the
-MI355X-side answer to "launch-bound inner loop -> HIP graph". `trainer.pretrain.pr_trainer.pr_rec_one_epoch(...,
-step_executor=...)` uses it when given one."""
+MI355X-side answer to "launch-bound inner loop -> HIP graph". The epoch loop (`trainer.epoch.run_epoch`, behind `pr_rec_one_epoch`,
+`ft_train_one_epoch` and their siblings) builds one on its first batch -- `trainer.epoch.auto_executor` keeps it on the model --
+or takes the one it is given (`pr_rec_one_epoch(..., step_executor=...)`)."""
 import contextlib
 import os
 
