@@ -748,6 +748,91 @@ def _branch_grad(g, rd, which, rps, mk, T, side, lp=None):
     return gs, (gs_lp if gs_lp is not None else cast(gs, T)), None
 
 
+# ----------------------------------------------------------------------------------------------------- patch convolutions
+# A Conv2d with kernel = stride = p evaluated only at the kept tokens is a GEMM on the gathered patch rows (gathering first is
+# equivalent because every step is per token). PatchEmbedFn, PatchProjFn, PatchEmbedNHWCFn, StridedConvTokensFn and
+# SwinFuseConvFn differ in how they gather and in what follows the GEMM; the gathers, the linear core and the embed tail are here.
+def _gather_nchw(x, ids_keep, patch):
+    """Patch rows of an NCHW f32 image at ids_keep (int64 [B,n_keep]; None: all L tokens in order), inner order (c,py,px) =
+    Conv2d weight.view(D,-1): -> (cols [B*n_keep, C*p*p] in the compute dtype, L, n_keep)."""
+    B, Cc, H, W = x.shape
+    L = (H // patch) * (W // patch)
+    n_keep = L if ids_keep is None else ids_keep.shape[1]
+    cols = torch.empty(B * n_keep, Cc * patch * patch, dtype=_compute_dtype, device=x.device)
+    call("evp_patchify", ptr(_chk(x.detach(), torch.float32)), ptr(ids_keep), B, Cc, H, W, patch, n_keep, ptr(cols), dt(cols),
+         stream_ptr())
+    return cols, L, n_keep
+
+
+def _gather_nhwc(x, ids_keep, patch, H, W):
+    """The same of a channels-last f32 token map [B, H*W, C]."""
+    B, Cin = x.shape[0], x.shape[-1]
+    L = (H // patch) * (W // patch)
+    n_keep = L if ids_keep is None else ids_keep.shape[1]
+    cols = torch.empty(B * n_keep, Cin * patch * patch, dtype=_compute_dtype, device=x.device)
+    call("evp_patchify_nhwc", ptr(_chk(x.detach().contiguous(), torch.float32)), ptr(ids_keep), B, H, W, Cin, patch, n_keep,
+         ptr(cols), dt(cols), stream_ptr())
+    return cols, L, n_keep
+
+
+def _scatter_nhwc(dcols, ids_keep, B, H, W, Cin, patch, n_keep):
+    """Adjoint of _gather_nhwc: dx [B, H*W, C] f32, zero at dropped patches."""
+    dx = torch.empty(B, H * W, Cin, dtype=torch.float32, device=dcols.device)
+    call("evp_unpatchify_nhwc", ptr(dcols), dt(dcols), ptr(ids_keep), B, H, W, Cin, patch, n_keep, 0, ptr(dx), stream_ptr())
+    return dx
+
+
+def _rows_linear(cols, w, b):
+    """-> (y [M,D] f32 = cols . w.view(D,Kc)^T + b, that weight view in the compute dtype)."""
+    M, Kc = cols.shape
+    D = w.shape[0]
+    wl = lp_weight(w).view(D, Kc)
+    y = torch.empty(M, D, dtype=torch.float32, device=cols.device)
+    gemm(cols, wl, y, M=M, N=D, K=Kc, bias=b)
+    return y, wl
+
+
+def _rows_linear_bwd(dy, db_from, cols, prm, need, wl=None, dcols_dtype=None):
+    """Backward of _rows_linear for prm = (w, b), need = their needs_input_grad flags: -> (dw, db, dcols). dW = dy^T cols, then
+    db = column sums of `db_from` (dy itself, or the f32 gradient it was cast from) -- this order is the order of the deferred
+    queue. With `wl`, also dcols [M,Kc] = dy . wl in `dcols_dtype` (default: dy's)."""
+    M, D = dy.shape
+    Kc = cols.shape[1]
+    dw = _wgrad(dy, cols, D, Kc, M, prm[0], prm[0].shape) if need[0] else None
+    db = _bgrad(db_from, prm[1]) if need[1] else None
+    dcols = None
+    if wl is not None:
+        dcols = torch.empty(M, Kc, dtype=dcols_dtype or dy.dtype, device=dy.device)
+        gemm(dy, wl, dcols, M=M, N=Kc, K=D, trans_b=True, ldb=Kc)
+    return dw, db, dcols
+
+
+def _embed_post(y, gamma, beta, pos, ids_keep, B, n_keep, L):
+    """GELU(LayerNorm_{eps 1e-5}(y)) + pos[token id] on the gathered rows: -> (out [M,D] f32, mean, rstd)."""
+    M, D = y.shape
+    out = torch.empty(M, D, dtype=torch.float32, device=y.device)
+    mean = torch.empty(M, dtype=torch.float32, device=y.device)
+    rstd = torch.empty(M, dtype=torch.float32, device=y.device)
+    pos2d = None if pos is None else _chk(pos.detach().view(L, D), torch.float32)
+    call("evp_embed_post_fwd", ptr(y), ptr(gamma), ptr(beta), ptr(pos2d), ptr(ids_keep), B, n_keep, L, D, 1e-5, ptr(out),
+         ptr(mean), ptr(rstd), stream_ptr())
+    return out, mean, rstd
+
+
+def _embed_post_bwd(g, y, gamma, beta, mean, rstd, dtype, params):
+    """-> (dy [M,D] in `dtype`, dgamma, dbeta). `params` as in _norm_grads: PatchEmbedFn passes its (gamma, beta) leaf
+    Parameters, so d gamma / d beta go to the deferred (grouped) column sums and come back None; PatchEmbedNHWCFn passes None and
+    has them reduced in the kernel. Nothing records a reason for that difference; removing it changes the deferred queue."""
+    M, D = y.shape
+    g = _chk(g.contiguous(), torch.float32).view(M, D)
+    dy = torch.empty(M, D, dtype=dtype, device=g.device)
+    ws, dgamma, dbeta, finish = _norm_grads(params, D, M, g.device)
+    call("evp_embed_post_bwd", ptr(g), ptr(y), ptr(gamma), ptr(beta), ptr(mean), ptr(rstd), M, D, ptr(dy), dt(dy), ptr(dgamma),
+         ptr(dbeta), ptr(ws), stream_ptr())
+    finish()
+    return dy, dgamma, dbeta
+
+
 # ----------------------------------------------------------------------------------------------------- autograd
 class ViTBlockFn(torch.autograd.Function):
     """Pre-LN transformer block (model/sub_module/vit_block.py:246-254) on a [B,N,D] f32 residual stream."""
@@ -848,50 +933,24 @@ class ViTBlockFn(torch.autograd.Function):
 
 class PatchEmbedFn(torch.autograd.Function):
     """Conv2d(k=s=p) + LayerNorm(eps 1e-5) + GELU (vit_block.py:60-68), + pos_embed, keeping only ids_keep tokens
-    (vit.py:110-115; gathering first is equivalent because every step is per token)."""
+    (vit.py:110-115)."""
 
     @staticmethod
     def forward(ctx, x, ids_keep, w, b, gamma, beta, pos, patch):
-        B, Cc, H, W = x.shape
-        L = (H // patch) * (W // patch)
-        n_keep = L if ids_keep is None else ids_keep.shape[1]
-        D = w.shape[0]
-        Kc = Cc * patch * patch
-        M = B * n_keep
-        T = _compute_dtype
-        dev = x.device
-        cols = torch.empty(M, Kc, dtype=T, device=dev)
-        call("evp_patchify", ptr(_chk(x.detach(), torch.float32)), ptr(ids_keep), B, Cc, H, W, patch, n_keep, ptr(cols),
-             dt(cols), stream_ptr())
-        wl = lp_weight(w).view(D, Kc)
-        y = torch.empty(M, D, dtype=torch.float32, device=dev)
-        gemm(cols, wl, y, M=M, N=D, K=Kc, bias=b)
-        out = torch.empty(M, D, dtype=torch.float32, device=dev)
-        mean = torch.empty(M, dtype=torch.float32, device=dev)
-        rstd = torch.empty(M, dtype=torch.float32, device=dev)
-        pos2d = None if pos is None else _chk(pos.detach().view(L, D), torch.float32)
-        call("evp_embed_post_fwd", ptr(y), ptr(gamma), ptr(beta), ptr(pos2d), ptr(ids_keep), B, n_keep, L, D, 1e-5,
-             ptr(out), ptr(mean), ptr(rstd), stream_ptr())
+        B = x.shape[0]
+        cols, L, n_keep = _gather_nchw(x, ids_keep, patch)
+        y, _ = _rows_linear(cols, w, b)
+        out, mean, rstd = _embed_post(y, gamma, beta, pos, ids_keep, B, n_keep, L)
         ctx.save_for_backward(cols, y, gamma, beta, mean, rstd)
-        ctx.wshape = tuple(w.shape)
         ctx.prm = (w, b)
         ctx.nprm = (gamma, beta)        # leaf parameters: targets of the deferred (grouped) column sums
-        return out.view(B, n_keep, D)
+        return out.view(B, n_keep, -1)
 
     @staticmethod
     def backward(ctx, g):
         cols, y, gamma, beta, mean, rstd = ctx.saved_tensors
-        M, D = y.shape
-        Kc = cols.shape[1]
-        dev = g.device
-        g = _chk(g.contiguous(), torch.float32).view(M, D)
-        dy = torch.empty(M, D, dtype=cols.dtype, device=dev)
-        ws, dgamma, dbeta, finish = _norm_grads(ctx.nprm, D, M, dev)
-        call("evp_embed_post_bwd", ptr(g), ptr(y), ptr(gamma), ptr(beta), ptr(mean), ptr(rstd), M, D, ptr(dy), dt(dy),
-             ptr(dgamma), ptr(dbeta), ptr(ws), stream_ptr())
-        finish()
-        dw = _wgrad(dy, cols, D, Kc, M, ctx.prm[0], ctx.wshape) if ctx.needs_input_grad[2] else None
-        db = _bgrad(dy, ctx.prm[1]) if ctx.needs_input_grad[3] else None
+        dy, dgamma, dbeta = _embed_post_bwd(g, y, gamma, beta, mean, rstd, cols.dtype, ctx.nprm)
+        dw, db, _ = _rows_linear_bwd(dy, dy, cols, ctx.prm, ctx.needs_input_grad[2:4])
         return None, None, dw, db, dgamma, dbeta, None, None
 
 
@@ -1281,98 +1340,50 @@ def enqueue_keys_dev(queue, keys, queue_ptr):
 class PatchEmbedNHWCFn(torch.autograd.Function):
     """PatchEmbed (Conv2d k=s=p -> LayerNorm(eps 1e-5) -> GELU, vit_block.py:60-68) on a channels-last token map
     x (B, H*W, C) f32, optionally restricted to ids_keep and with a positional table: the conv is a GEMM on the
-    gathered patch matrix (convvit.py:22-25,141,153)."""
+    gathered patch matrix (convvit.py:22-25,141,153). dx only where x requires a gradient."""
 
     @staticmethod
     def forward(ctx, x, ids_keep, w, b, gamma, beta, pos, patch, H, W):
-        B = x.shape[0]
-        Cin = x.shape[-1]
-        D = w.shape[0]
-        L = (H // patch) * (W // patch)
-        n_keep = L if ids_keep is None else ids_keep.shape[1]
-        Kc = Cin * patch * patch
-        M = B * n_keep
-        T = _compute_dtype
-        dev = x.device
-        xin = _chk(x.detach().contiguous(), torch.float32)
-        cols = torch.empty(M, Kc, dtype=T, device=dev)
-        call("evp_patchify_nhwc", ptr(xin), ptr(ids_keep), B, H, W, Cin, patch, n_keep, ptr(cols), dt(cols), stream_ptr())
-        wl = lp_weight(w).view(D, Kc)
-        y = torch.empty(M, D, dtype=torch.float32, device=dev)
-        gemm(cols, wl, y, M=M, N=D, K=Kc, bias=b)
-        out = torch.empty(M, D, dtype=torch.float32, device=dev)
-        mean = torch.empty(M, dtype=torch.float32, device=dev)
-        rstd = torch.empty(M, dtype=torch.float32, device=dev)
-        pos2d = None if pos is None else _chk(pos.detach().view(L, D), torch.float32)
-        call("evp_embed_post_fwd", ptr(y), ptr(gamma), ptr(beta), ptr(pos2d), ptr(ids_keep), B, n_keep, L, D, 1e-5, ptr(out),
-             ptr(mean), ptr(rstd), stream_ptr())
+        B, Cin = x.shape[0], x.shape[-1]
+        cols, L, n_keep = _gather_nhwc(x, ids_keep, patch, H, W)
+        y, wl = _rows_linear(cols, w, b)
+        out, mean, rstd = _embed_post(y, gamma, beta, pos, ids_keep, B, n_keep, L)
         ctx.save_for_backward(cols, y, gamma, beta, mean, rstd, wl, ids_keep)
-        ctx.cfg = (B, H, W, Cin, D, patch, n_keep, Kc, tuple(w.shape), x.requires_grad)
+        ctx.geom = (B, H, W, Cin, patch, n_keep)
+        ctx.need_dx = x.requires_grad
         ctx.prm = (w, b)
-        return out.view(B, n_keep, D)
+        return out.view(B, n_keep, -1)
 
     @staticmethod
     def backward(ctx, g):
         cols, y, gamma, beta, mean, rstd, wl, ids_keep = ctx.saved_tensors
-        B, H, W, Cin, D, patch, n_keep, Kc, wshape, need_dx = ctx.cfg
-        M = B * n_keep
-        dev = g.device
-        g = _chk(g.contiguous(), torch.float32).view(M, D)
-        dy = torch.empty(M, D, dtype=cols.dtype, device=dev)
-        ws, dgamma, dbeta, _ = _norm_grads(None, D, M, dev)     # this form reduces d gamma / d beta in the kernel: nothing deferred
-        call("evp_embed_post_bwd", ptr(g), ptr(y), ptr(gamma), ptr(beta), ptr(mean), ptr(rstd), M, D, ptr(dy), dt(dy), ptr(dgamma),
-             ptr(dbeta), ptr(ws), stream_ptr())
-        dw = _wgrad(dy, cols, D, Kc, M, ctx.prm[0], wshape) if ctx.needs_input_grad[2] else None
-        db = _bgrad(dy, ctx.prm[1]) if ctx.needs_input_grad[3] else None
-        dx = None
-        if need_dx:
-            dcols = torch.empty(M, Kc, dtype=cols.dtype, device=dev)
-            gemm(dy, wl, dcols, M=M, N=Kc, K=D, trans_b=True, ldb=Kc)
-            dx = torch.empty(B, H * W, Cin, dtype=torch.float32, device=dev)
-            call("evp_unpatchify_nhwc", ptr(dcols), dt(dcols), ptr(ids_keep), B, H, W, Cin, patch, n_keep, 0, ptr(dx), stream_ptr())
+        dy, dgamma, dbeta = _embed_post_bwd(g, y, gamma, beta, mean, rstd, cols.dtype, None)
+        dw, db, dcols = _rows_linear_bwd(dy, dy, cols, ctx.prm, ctx.needs_input_grad[2:4], wl if ctx.need_dx else None)
+        dx = _scatter_nhwc(dcols, ids_keep, *ctx.geom) if ctx.need_dx else None
         return dx, None, dw, db, dgamma, dbeta, None, None, None, None
 
 
 class StridedConvTokensFn(torch.autograd.Function):
     """Conv2d(k=s=p) + bias on a channels-last map, evaluated only at the tokens in ids_keep (the multi-scale fusion
-    convs stage1/2_output_decode followed by the gather, convvit.py:137-140,149-151)."""
+    convs stage1/2_output_decode followed by the gather, convvit.py:137-140,149-151). dx always."""
 
     @staticmethod
     def forward(ctx, x, ids_keep, w, b, patch, H, W):
         B, _, Cin = x.shape
-        D = w.shape[0]
-        L = (H // patch) * (W // patch)
-        n_keep = L if ids_keep is None else ids_keep.shape[1]
-        Kc = Cin * patch * patch
-        M = B * n_keep
-        T = _compute_dtype
-        dev = x.device
-        cols = torch.empty(M, Kc, dtype=T, device=dev)
-        call("evp_patchify_nhwc", ptr(_chk(x.detach().contiguous(), torch.float32)), ptr(ids_keep), B, H, W, Cin, patch, n_keep,
-             ptr(cols), dt(cols), stream_ptr())
-        wl = lp_weight(w).view(D, Kc)
-        y = torch.empty(M, D, dtype=torch.float32, device=dev)
-        gemm(cols, wl, y, M=M, N=D, K=Kc, bias=b)
+        cols, _, n_keep = _gather_nhwc(x, ids_keep, patch, H, W)
+        y, wl = _rows_linear(cols, w, b)
         ctx.save_for_backward(cols, wl, ids_keep)
-        ctx.cfg = (B, H, W, Cin, D, patch, n_keep, Kc, tuple(w.shape))
+        ctx.geom = (B, H, W, Cin, patch, n_keep)
         ctx.prm = (w, b)
-        return y.view(B, n_keep, D)
+        return y.view(B, n_keep, -1)
 
     @staticmethod
     def backward(ctx, g):
         cols, wl, ids_keep = ctx.saved_tensors
-        B, H, W, Cin, D, patch, n_keep, Kc, wshape = ctx.cfg
-        M = B * n_keep
-        dev = g.device
-        g2 = _chk(g.contiguous(), torch.float32).view(M, D)
-        gl = cast(g2, cols.dtype)
-        dw = _wgrad(gl, cols, D, Kc, M, ctx.prm[0], wshape) if ctx.needs_input_grad[2] else None
-        db = _bgrad(g2, ctx.prm[1]) if ctx.needs_input_grad[3] else None
-        dcols = torch.empty(M, Kc, dtype=cols.dtype, device=dev)
-        gemm(gl, wl, dcols, M=M, N=Kc, K=D, trans_b=True, ldb=Kc)
-        dx = torch.empty(B, H * W, Cin, dtype=torch.float32, device=dev)
-        call("evp_unpatchify_nhwc", ptr(dcols), dt(dcols), ptr(ids_keep), B, H, W, Cin, patch, n_keep, 0, ptr(dx), stream_ptr())
-        return dx, None, dw, db, None, None, None
+        g2d = _chk(g.contiguous(), torch.float32).view(cols.shape[0], -1)
+        gl = cast(g2d, cols.dtype)
+        dw, db, dcols = _rows_linear_bwd(gl, g2d, cols, ctx.prm, ctx.needs_input_grad[2:4], wl)
+        return _scatter_nhwc(dcols, ids_keep, *ctx.geom), None, dw, db, None, None, None
 
 
 class AddPosGatherFn(torch.autograd.Function):
@@ -1510,74 +1521,51 @@ class GatherRowsFn(torch.autograd.Function):
 
 class PatchProjFn(torch.autograd.Function):
     """Conv2d(k=s=patch) of an NCHW f32 image evaluated only at the tokens `ids_keep` (int64 [B,n_keep]), returned as
-    f32 tokens [B,n_keep,D] (swin_block.py:58-62 before its norm; gathering first is equivalent, every step is per token)."""
+    f32 tokens [B,n_keep,D] (swin_block.py:58-62 before its norm)."""
 
     @staticmethod
     def forward(ctx, x, ids_keep, w, b, patch):
-        B, Cc, H, W = x.shape
-        L = (H // patch) * (W // patch)
-        n_keep = L if ids_keep is None else ids_keep.shape[1]
-        D = w.shape[0]
-        Kc = Cc * patch * patch
-        M = B * n_keep
-        cols = torch.empty(M, Kc, dtype=_compute_dtype, device=x.device)
-        call("evp_patchify", ptr(_chk(x.detach(), torch.float32)), ptr(ids_keep), B, Cc, H, W, patch, n_keep, ptr(cols),
-             dt(cols), stream_ptr())
-        y = torch.empty(M, D, dtype=torch.float32, device=x.device)
-        gemm(cols, lp_weight(w).view(D, Kc), y, M=M, N=D, K=Kc, bias=b)
+        cols, _, n_keep = _gather_nchw(x, ids_keep, patch)
+        y, _ = _rows_linear(cols, w, b)
         ctx.save_for_backward(cols)
-        ctx.wshape = tuple(w.shape)
         ctx.prm = (w, b)
-        return y.view(B, n_keep, D)
+        return y.view(x.shape[0], n_keep, -1)
 
     @staticmethod
     def backward(ctx, g):
         (cols,) = ctx.saved_tensors
-        M, Kc = cols.shape
-        D = ctx.wshape[0]
-        g2d = _chk(g.contiguous(), torch.float32).view(M, D)
+        g2d = _chk(g.contiguous(), torch.float32).view(cols.shape[0], -1)
         gl = cast(g2d, cols.dtype)
-        dw = _wgrad(gl, cols, D, Kc, M, ctx.prm[0], ctx.wshape) if ctx.needs_input_grad[2] else None
-        db = _bgrad(g2d, ctx.prm[1]) if ctx.needs_input_grad[3] else None
+        dw, db, _ = _rows_linear_bwd(gl, g2d, cols, ctx.prm, ctx.needs_input_grad[2:4])
         return None, None, dw, db, None
 
 
 class SwinFuseConvFn(torch.autograd.Function):
     """swin.py:201-208: scatter the visible stage tokens into a zero R x R grid, Conv2d(k, stride k) down to the
     decoder grid, gather each sample's ids_keep cells -- formed directly as the [B*K, C*k*k] patch rows of the kept
-    cells times weight.view(out, C*k*k)."""
+    cells times weight.view(out, C*k*k). The gather and its adjoint work in f32."""
 
     @staticmethod
     def forward(ctx, x, w, b, tokmap, coords, ids_keep, ids_restore, R, k):
         B, n, C = x.shape
         K = ids_keep.shape[1]
-        Dout = w.shape[0]
-        Kc = C * k * k
-        M = B * K
-        A = torch.empty(M, Kc, dtype=torch.float32, device=x.device)
+        A = torch.empty(B * K, C * k * k, dtype=torch.float32, device=x.device)
         call("evp_swin_fuse_gather_f32", ptr(_chk(x.detach().contiguous(), torch.float32)), ptr(_chk(tokmap, torch.int32)),
              ptr(_chk(ids_keep, torch.int64)), ptr(A), B, n, K, C, R, k, stream_ptr())
         Al = cast(A, _compute_dtype)
-        wl = lp_weight(w).view(Dout, Kc)
-        y = torch.empty(M, Dout, dtype=torch.float32, device=x.device)
-        gemm(Al, wl, y, M=M, N=Dout, K=Kc, bias=b)
+        y, wl = _rows_linear(Al, w, b)
         ctx.save_for_backward(Al, wl, coords, ids_restore)
-        ctx.dims = (B, n, K, C, R, k, Dout, Kc)
-        ctx.wshape = tuple(w.shape)
+        ctx.dims = (B, n, K, C, R, k)
         ctx.prm = (w, b)
-        return y.view(B, K, Dout)
+        return y.view(B, K, -1)
 
     @staticmethod
     def backward(ctx, g):
         Al, wl, coords, ids_restore = ctx.saved_tensors
-        B, n, K, C, R, k, Dout, Kc = ctx.dims
-        M = B * K
-        g2d = _chk(g.contiguous(), torch.float32).view(M, Dout)
+        B, n, K, C, R, k = ctx.dims
+        g2d = _chk(g.contiguous(), torch.float32).view(B * K, -1)
         gl = cast(g2d, Al.dtype)
-        dw = _wgrad(gl, Al, Dout, Kc, M, ctx.prm[0], ctx.wshape) if ctx.needs_input_grad[1] else None
-        db = _bgrad(g2d, ctx.prm[1]) if ctx.needs_input_grad[2] else None
-        dA = torch.empty(M, Kc, dtype=torch.float32, device=g.device)
-        gemm(gl, wl, dA, M=M, N=Kc, K=Dout, trans_b=True, ldb=Kc)
+        dw, db, dA = _rows_linear_bwd(gl, g2d, Al, ctx.prm, ctx.needs_input_grad[1:3], wl, torch.float32)
         dx = torch.empty(B, n, C, dtype=torch.float32, device=g.device)
         call("evp_swin_fuse_gather_bwd_f32", ptr(dA), ptr(coords), ptr(ids_restore), ptr(dx), B, n, K, C, R, k, stream_ptr())
         return dx, dw, db, None, None, None, None, None, None
