@@ -15,6 +15,7 @@ CSRC = os.path.join(_HERE, "csrc")
 
 ABI_VERSION = 5            # include/evtpretrain.h EVP_ABI_VERSION: checked when the library is loaded (EVP_LIB overrides included)
 EVP_F32, EVP_BF16 = 0, 1
+CLS_METRICS_SINGLE_ROWS, CLS_METRICS_WS = 1024, 3072      # include/evtpretrain.h EVP_CLS_METRICS_*
 ACT_NONE, ACT_GELU, ACT_DGELU, ACT_RELU, ACT_DRELU = 0, 1, 2, 3, 4
 
 _vp, _i, _i64, _f, _d = C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_double
@@ -115,6 +116,7 @@ SIGNATURES = {
     "evp_token_mean_fwd": [_vp, _i, _i, _i, _vp, _vp],
     "evp_token_mean_bwd": [_vp, _i, _i, _i, _vp, _vp],
     "evp_rows_scale_f32": [_vp, _vp, _f, _vp, _i64, _i, _i, _vp, _vp, _vp],
+    "evp_cls_metrics": [_vp, _vp, _i64, _i, _i64, _vp, _vp, _i64, _vp, _vp],
     "evp_dropout_fwd": [_vp, _i, _vp, _vp, _i64, _f, C.c_uint64, _vp, C.c_uint64, _vp],
     "evp_dropout_apply": [_vp, _i, _vp, _vp, _i64, _f, _vp],
     "evp_abi_version": [],

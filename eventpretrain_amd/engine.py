@@ -534,3 +534,131 @@ class GraphedStep:
         if self._tables_read is None:
             self._tables_read = torch.cuda.Event()
         self._tables_read.record()
+
+
+class MetricsTable:
+    """The device table ops.cls_metrics fills ({loss, acc1, acc5} per batch) and the device cursor that names its next free slot.
+    The host counts the batches it has queued; read(n) brings n slots back with ONE read-back and rewinds the cursor."""
+
+    def __init__(self, device, capacity=4096):
+        self.capacity = int(capacity)
+        if self.capacity < 1:
+            raise ValueError("MetricsTable needs at least one slot")
+        self.rows = torch.zeros(self.capacity, 3, dtype=torch.float32, device=device)
+        self.cursor = torch.zeros(1, dtype=torch.int64, device=device)
+
+    def rewind(self):
+        self.cursor.zero_()
+
+    def read(self, n):
+        """-> the first n slots as [[loss, acc1, acc5], ...] (host floats), in the order they were written; cursor <- 0."""
+        vals = self.rows[:n].tolist() if n else []
+        self.rewind()
+        return vals
+
+
+class GraphedEval:
+    """The forward-only sibling of GraphedStep: `forward(model, *static_inputs)` under torch.no_grad() and model.eval(), warmed up,
+    captured once as a HIP graph (through _GraphSeq, as the training step is) and replayed per batch. For classification
+    fine-tuning the forward is `model(x)[-2]` followed by ops.cls_metrics into `table` (a MetricsTable the forward closes over; the
+    executor rewinds it after its own warm-up and capture), so that an evaluation loop makes no host round-trip per batch.
+
+        .inputs               the static input buffers
+        .run(*tensors)        copy into them (same shapes) and replay
+        .eager_with(*tensors) the same calls uncaptured, for a batch of another shape (the short last batch of a validation set)
+        .current(model)       see there: call once before a run of replays when the weights may have changed since the last one
+
+    The graph reads parameters, module buffers and bf16 weight shadows (ops.lp_weight) BY ADDRESS. FusedAdamW updates between two
+    evaluations need nothing: it writes the same parameter and shadow buffers. Weights written behind its back (load_state_dict)
+    leave the shadows stale; .current() re-casts them in place. If capture fails the executor says so (`note`) and runs eagerly."""
+
+    def __init__(self, model, forward, static_inputs, table=None, use_graph=True, warmup=2):
+        self.model, self.forward, self.table = model, forward, table
+        self.inputs = [t for t in static_inputs]
+        self.graph = self.out = None
+        self.note = "eager"
+        self.captures = self.replays = self.eager_calls = 0
+        self._dtype = ops.get_compute_dtype()
+        if use_graph:
+            self._capture(max(1, warmup))
+        self._addresses = self._addresses_now()
+        # what else the captured launches read by address: a Swin backbone's cached window-plan tables
+        self._keep = list(getattr(getattr(model, "backbone", None), "_plans", {}).values())
+        if table is not None:
+            table.rewind()
+
+    def _call(self, inputs):
+        self.model.eval()
+        with torch.no_grad():
+            return self.forward(self.model, *inputs)
+
+    def _capture(self, warmup):
+        import gc
+        side = torch.cuda.Stream()
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):       # warm up on the capture stream: allocator, bf16 shadows, the model's cached tables
+            for _ in range(warmup):
+                self._call(self.inputs)
+        torch.cuda.current_stream().wait_stream(side)
+        torch.cuda.synchronize()
+        try:
+            seq = _GraphSeq(side)
+            gc.collect()
+            torch.cuda.empty_cache()
+            with torch.cuda.stream(side):
+                seq.begin()
+                try:
+                    self.out = self._call(self.inputs)
+                    seq.end()
+                except BaseException:
+                    seq.abort()
+                    raise
+            self.graph, self.note = seq, "hip-graph"
+            self.captures += 1
+        except Exception as e:               # keep evaluating; say what happened
+            if os.environ.get("EVP_RAISE_CAPTURE"):
+                import traceback
+                traceback.print_exc()
+            self.graph = self.out = None
+            self.note = "eager (graph capture failed: %r)" % (e,)
+        torch.cuda.synchronize()
+
+    def _addresses_now(self):
+        """(address of every parameter and buffer, address of every CURRENT bf16 shadow or 0): what a captured forward reads."""
+        own = [t.data_ptr() for t in self.model.parameters()] + [b.data_ptr() for b in self.model.buffers()]
+        lp = []
+        for p in self.model.parameters():
+            sh = getattr(p, "_evp_lp", None)
+            lp.append(sh.data_ptr() if (sh is not None and getattr(p, "_evp_lp_version", -1) == p._version) else 0)
+        return own, lp
+
+    def current(self, model=None):
+        """Bring the captured graph up to date with the model, or say that it cannot be: shadows whose parameter was written outside
+        FusedAdamW (`_version` moved) are re-cast INTO THEIR EXISTING BUFFERS; then False if the model, the compute dtype, or the
+        address of any parameter, buffer or shadow the capture read has changed -- the caller builds a new executor."""
+        if (model is not None and model is not self.model) or ops.get_compute_dtype() != self._dtype:
+            return False
+        own, lp = self._addresses
+        params = list(self.model.parameters())
+        if len(params) != len(lp):
+            return False
+        stale = [p for p, a in zip(params, lp)
+                 if a and getattr(p, "_evp_lp", None) is not None and p._evp_lp.data_ptr() == a and p._evp_lp_version != p._version]
+        ops.refresh_lp_shadows(stale)
+        return self._addresses_now() == (own, lp)
+
+    def run(self, *tensors):
+        for dst, src in zip(self.inputs, tensors):
+            if src is not dst:
+                dst.copy_(src, non_blocking=True)
+        if self.graph is None:
+            self.eager_calls += 1
+            self.out = self._call(self.inputs)
+        else:
+            self.graph.replay()
+            self.replays += 1
+        return self.out
+
+    def eager_with(self, *tensors):
+        self.eager_calls += 1
+        return self._call(list(tensors))

@@ -1803,3 +1803,30 @@ class CrossEntropyFn(torch.autograd.Function):
         out = dlog.clone()
         call("evp_scale_f32", ptr(out), ptr(_chk(g.contiguous().view(1), torch.float32)), out.numel(), stream_ptr())
         return out, None, None
+
+
+def cls_metrics(pred, label, table, cursor):
+    """The evaluation record of one batch on the device (evp_cls_metrics; reference ft_cls_trainer.py:152-164): with s = cursor[0],
+    table[s] = {mean cross entropy, top-1 %, top-5 %} of f32 logits `pred` [R, n_cls] against int64 `label` [R], then cursor[0] = s + 1;
+    a full table (s >= table.shape[0]) is left alone. `table` f32 [capacity, 3] and `cursor` int64 [1] live in device memory, so a
+    captured graph fills slot after slot with no host round-trip. The rows are read in place through pred.stride(0): the padded head
+    output of LinearFn is not copied."""
+    for t in (pred, label, table, cursor):
+        if not t.is_cuda:
+            raise _lib.EvpError("cls_metrics: tensor is not in device memory; eventpretrain_amd has no CPU path")
+    if pred.dim() != 2 or pred.dtype != torch.float32:
+        raise _lib.EvpError(f"cls_metrics: logits must be float32 [R, n_cls] (got {pred.dtype} {tuple(pred.shape)})")
+    R, n_cls = pred.shape
+    pred = pred.detach()
+    ld = pred.stride(0) if R > 1 else n_cls
+    # in place only where every row, the last included, has ld floats behind it in the storage (a column slice of a padded matrix)
+    room = pred.untyped_storage().nbytes() // 4 - pred.storage_offset()
+    if pred.stride(1) != 1 or ld < n_cls or R * ld > room:
+        pred, ld = pred.contiguous(), n_cls
+    if tuple(label.shape) != (R,):
+        raise _lib.EvpError(f"cls_metrics: expected {R} labels, got {tuple(label.shape)}")
+    if table.dim() != 2 or table.shape[1] != 3 or cursor.numel() != 1:
+        raise _lib.EvpError("cls_metrics: table must be float32 [capacity, 3] and cursor one int64")
+    ws = torch.empty(_lib.CLS_METRICS_WS, dtype=torch.float32, device=pred.device) if R > _lib.CLS_METRICS_SINGLE_ROWS else None
+    call("evp_cls_metrics", pred.data_ptr(), ptr(_chk(label, torch.int64)), R, n_cls, ld, ptr(_chk(cursor, torch.int64)),
+         ptr(_chk(table, torch.float32)), table.shape[0], ptr(ws), stream_ptr())

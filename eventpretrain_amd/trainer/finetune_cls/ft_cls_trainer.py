@@ -8,7 +8,7 @@ import torch
 
 from ... import ops
 from ...utils import misc
-from ..epoch import auto_executor, run_epoch
+from ..epoch import DevicePrefetcher, auto_executor, run_epoch
 
 
 def _forward(args, model, x):
@@ -61,12 +61,73 @@ def ft_train_one_epoch(args, model, data_loader, optimizer, epoch, loss_scaler, 
                      build_executor=build, clip_grad=getattr(args, "clip_grad", None), meter_divided=True)
 
 
-@torch.no_grad()
-def ft_val(args, model, data_loader, epoch, dataset_name="origin", evrepsl_model=None):
-    if evrepsl_model is not None or getattr(args, "use_evrepsl", False):
-        raise NotImplementedError("EvRepSL preprocessing is out of scope (SURVEY.md 2)")
-    model.eval()
-    logger = misc.MetricLogger(delimiter="  ")
+EVAL_TABLE_SLOTS = 4096      # slots of the device metrics table of a captured evaluation (args.eval_table_slots overrides)
+
+
+def auto_eval_executor(args, model, batch_tensors):
+    """The captured evaluation forward (backbone -> token mean -> head -> ops.cls_metrics into a device table) ft_val builds on its
+    first batch and keeps on the model, in `model._evp_auto_eval` as (key, executor), as trainer.epoch.auto_executor keeps the
+    training step: one engine.GraphedEval per (compute dtype, table slots, shapes and dtypes of the batch), re-used by every later
+    ft_val on the model -- the ten validation sets of an N-ImageNet epoch replay one capture -- as long as executor.current(model)
+    holds (asked here, once per ft_val call); weights that moved to other addresses build a new one."""
+    from ...engine import GraphedEval, MetricsTable
+    slots = int(getattr(args, "eval_table_slots", None) or EVAL_TABLE_SLOTS)
+    key = (str(ops.get_compute_dtype()), slots, tuple((tuple(t.shape), str(t.dtype)) for t in batch_tensors))
+    cached = getattr(model, "_evp_auto_eval", None)
+    if cached is not None and cached[0] == key and cached[1].current(model):
+        cached[1].table.rewind()
+        return cached[1]
+    table = MetricsTable(batch_tensors[0].device, slots)
+    fwd = lambda m, x_, y_: ops.cls_metrics(m(x_)[-2], y_, table.rows, table.cursor)
+    model._evp_auto_eval = (key, GraphedEval(model, fwd, [t.clone() for t in batch_tensors], table=table))
+    return model._evp_auto_eval[1]
+
+
+def _use_captured_eval(args, model):
+    """ft_val's captured form stands in for its eager loop on a CUDA device unless the caller opted out (`args.graph_step = False`,
+    `args.sync_every_step = True`), replaced `forward` on the instance, or asked for per-step visualisation."""
+    if not str(args.device).startswith("cuda") or not getattr(args, "graph_step", True) or getattr(args, "sync_every_step", False):
+        return False
+    return "forward" not in vars(model) and not (getattr(args, "test_experiment", False) and getattr(args, "visualize", False))
+
+
+def _val_loop_deferred(args, data_loader, logger, executor_for, with_acc5):
+    """The evaluation loop with no host round-trip per batch: every batch is one executor.run (a HIP-graph replay; eager_with for a
+    batch of another shape) that leaves {loss, acc1, acc5} in the executor's device table; the table is read back and rewound when
+    a progress line is due, when it is full and at the end of the loader, and every slot becomes one update per meter, in batch
+    order -- global_avg, the smoothed window and the returned dict are what per-batch updates give, the reference's equal weight
+    of a short last batch included. -> host seconds spent queueing the forwards."""
+    n_iter = len(data_loader)
+    executor, pending, infer_time = None, 0, 0.0
+
+    def flush():
+        for loss, acc1, acc5 in executor.table.read(pending):
+            logger.update(loss_cls=loss)
+            logger.update(acc1=acc1)
+            if with_acc5:
+                logger.update(acc5=acc5)
+        return 0
+
+    for it, (events_voxel_grid, label, image_name) in enumerate(logger.log_every(args, data_loader, args.print_freq, "Test:")):
+        tensors = [events_voxel_grid.to(args.device, non_blocking=True), label.to(args.device, non_blocking=True)]
+        if executor is None:
+            executor = executor_for(tensors)
+        t0 = time.time()
+        if all(tuple(t.shape) == tuple(s.shape) for t, s in zip(tensors, executor.inputs)):
+            executor.run(*tensors)
+        else:
+            executor.eager_with(*tensors)
+        infer_time += time.time() - t0
+        pending += 1
+        if (it + 1) % args.print_freq == 0 or pending >= executor.table.capacity or it + 1 == n_iter:
+            pending = flush()
+    if pending:              # (a loader that yields more batches than len() promised)
+        flush()
+    return infer_time
+
+
+def _val_loop_eager(args, model, data_loader, logger, with_acc5):
+    """The reference's loop as it stands: eager forward, cross entropy and top-k on the device, three read-backs per batch."""
     infer_time = 0.0
     for events_voxel_grid, label, image_name in logger.log_every(args, data_loader, args.print_freq, "Test:"):
         events_voxel_grid = events_voxel_grid.to(args.device, non_blocking=True)
@@ -76,13 +137,36 @@ def ft_val(args, model, data_loader, epoch, dataset_name="origin", evrepsl_model
         infer_time += time.time() - t0
         loss_cls = ops.CrossEntropyFn.apply(pred, label)
         logger.update(loss_cls=loss_cls.item())
-        if getattr(args, "dataset_type", "") != "n-cars":
+        if with_acc5:
             acc1, acc5 = _topk_accuracy(pred, label, topk=(1, 5))
             logger.update(acc1=acc1.item())
             logger.update(acc5=acc5.item())
         else:
             (acc1,) = _topk_accuracy(pred, label, topk=(1,))
             logger.update(acc1=acc1.item())
+    return infer_time
+
+
+@torch.no_grad()
+def ft_val(args, model, data_loader, epoch, dataset_name="origin", evrepsl_model=None):
+    """One evaluation pass (reference ft_cls_trainer.py:110-192) -> {loss_cls, acc1, acc5} (no acc5 for n-cars), each the mean over
+    batches of the per-batch value. On the GPU the forward and its metrics run as HIP-graph replays (auto_eval_executor), the
+    per-batch values stay in a device table between progress lines (_val_loop_deferred) and batch i + 1 is uploaded while batch i
+    runs; `args.graph_step = False` or `args.sync_every_step = True` give the eager loop with its three read-backs per batch, which
+    is also what a CPU device runs. The reported "average inference time" is host time around the forward call in both forms: the
+    reference does not synchronise there either, so it times the enqueue (in the captured form, of the replay with its metrics)."""
+    if evrepsl_model is not None or getattr(args, "use_evrepsl", False):
+        raise NotImplementedError("EvRepSL preprocessing is out of scope (SURVEY.md 2)")
+    model.eval()
+    logger = misc.MetricLogger(delimiter="  ")
+    with_acc5 = getattr(args, "dataset_type", "") != "n-cars"
+    if _use_captured_eval(args, model):
+        loader = data_loader
+        if getattr(args, "prefetch_to_device", True) and not getattr(data_loader, "yields_device_batches", False):
+            loader = DevicePrefetcher(data_loader, args.device)
+        infer_time = _val_loop_deferred(args, loader, logger, lambda t: auto_eval_executor(args, model, t), with_acc5)
+    else:
+        infer_time = _val_loop_eager(args, model, data_loader, logger, with_acc5)
     logger.synchronize_between_processes()
     if "acc5" in logger.meters:
         print("* Acc@1 {:.3f} Acc@5 {:.3f} loss_cls {:.3f}".format(logger.acc1.global_avg, logger.acc5.global_avg, logger.loss_cls.global_avg))

@@ -506,6 +506,28 @@ int evp_frame_augment_f32(const float *in, const int32_t *params, float *out, in
 int evp_token_mean_fwd(const float *x, int B, int N, int D, float *out, void *stream);
 int evp_token_mean_bwd(const float *g, int B, int N, int D, float *dx, void *stream);
 
+/* ------------------------------------------------------------------------------------------------ K25 evaluation metrics
+ * The per-batch record of the reference's evaluation loop (trainer/finetune_cls/ft_cls_trainer.py:152-164: nn.CrossEntropyLoss()
+ * and timm's `accuracy(pred, label, topk=(1, 5))`; timm is not vendored in the reference, its published rule is restated) computed
+ * on the device and written into a device-resident table, so that an evaluation loop reads nothing back per batch.
+ * logits float32 [R,ld] (n_cls valid columns), labels int64 [R], table float32 [capacity,3], cursor one int64 in DEVICE memory.
+ * With s = *cursor: if 0 <= s < capacity the call writes table[s] = {loss, acc1, acc5} and then *cursor = s + 1; otherwise it
+ * writes nothing and leaves the cursor alone. The slot index lives on the device: a captured HIP graph advances it on replay.
+ *   loss    mean_r(logsumexp(logits[r,:n_cls]) - logits[r,label[r]])   (mean reduction, no smoothing)
+ *   rank_r  the number of columns j < n_cls, j != label[r], that come before the label's column in the order
+ *           torch.topk(largest=True) uses: a larger value first, NaN larger than every number, equal values (NaN against NaN
+ *           included) lower index first. Comparisons of the stored float32 values only: for tie-free rows the hit counts are
+ *           torch.topk's exactly.
+ *   acc_k   (100 / R) * #{r : rank_r < min(k, n_cls)} for k = 1, 5  (timm: maxk = min(max(topk), n_cls); with two classes acc5
+ *           is the top-2 rate)
+ * A label outside [0, n_cls) reads nothing out of range: its row is a miss for both k and the batch's loss is NaN (the
+ * reference asserts on the device instead). R <= EVP_CLS_METRICS_SINGLE_ROWS: one launch, workspace may be NULL; more rows: two
+ * launches and workspace float32 [EVP_CLS_METRICS_WS]. No atomics: the same inputs give the same bits. */
+#define EVP_CLS_METRICS_SINGLE_ROWS 1024
+#define EVP_CLS_METRICS_WS 3072
+int evp_cls_metrics(const float *logits, const int64_t *labels, int64_t R, int n_cls, int64_t ld, int64_t *cursor, float *table,
+                    int64_t capacity, float *workspace, void *stream);
+
 /* ------------------------------------------------------------------------------------------------ K24 stochastic depth / dropout
  * The regularisers of the fine-tuning recipe (main_finetune_cls.py:151-153, drop_path_rate 0.1 by default).
  * DropPath (timm 0.3.2 `drop_path`; model/sub_module/vit_block.py:241,252-253, conv_block.py:35,43-49, swin_block.py:257,270-271):
