@@ -717,15 +717,17 @@ def rows_scale(x, u, keep_prob, rows_per_sample, res=None, want_out=True, want_l
     return out, lp
 
 
-def _branch_residual(a, w, bias, res, M, N, K, rd, which, rps, key):
-    """Residual-stream output of one branch: res + drop_path(dropout(a . w^T + bias)). rd None: fused in the GEMM epilogue."""
+def _branch_residual(a, w, bias, res, rd, which, rps, key):
+    """Residual-stream output of one branch, a [M,K] and w [N,K]: res + drop_path(dropout(a . w^T + bias)). rd None: fused in the
+    GEMM epilogue. `key`: the branch's dropout mask in rd.masks; None for a branch without dropout of its own."""
+    (M, K), N = a.shape, w.shape[0]
     out = torch.empty(M, N, dtype=torch.float32, device=a.device)
     if rd is None:
         gemm(a, w, out, M=M, N=N, K=K, bias=bias, residual=res)
         return out, None
     gemm(a, w, out, M=M, N=N, K=K, bias=bias)
     mk = None
-    if rd.drop > 0:
+    if key is not None and rd.drop > 0:
         out, mk = dropout_fwd(out, rd, key)
     y, _ = rows_scale(out, rd.u[which], rd.keep_prob, rps, res=res)
     return y, mk
@@ -746,6 +748,57 @@ def _branch_grad(g, rd, which, rps, mk, T, side, lp=None):
     if mk is not None:
         gs = dropout_bwd(gs, mk, rd.drop)
     return gs, (gs_lp if gs_lp is not None else cast(gs, T)), None
+
+
+def _linear_bwd(dy, x, wl, wparam, bparam, need_w, need_b, dy_f32=None, dy_colsum=None, act=ACT_NONE, aux=None):
+    """Backward of a Linear (or 1x1 conv) inside a residual block, y [M,N] = x [M,K] . wl^T + bias with wl [N,K] = wparam in the
+    compute dtype: -> (dW in wparam's shape, db, dx [M,K] in dy's dtype). The weight gradient, with the bias on the same problem
+    (_wgrad_bias; dy_f32 / dy_colsum as there), is queued first -- the order of the deferred queue -- then dx = act'(dy . wl) is
+    launched (`act`, `aux`: the GEMM epilogue's). LinearFn, LinearBNFn and _rows_linear_bwd are not on this: they take _wgrad and
+    _bgrad, the bias apart from the weight-gradient problem, and moving them here would change the deferred queue."""
+    (M, N), K = dy.shape, x.shape[1]
+    dw, db = _wgrad_bias(dy, x, N, K, M, wparam, bparam, need_w, need_b, dy_f32=dy_f32, shape=tuple(wparam.shape), dy_colsum=dy_colsum)
+    dx = torch.empty(M, K, dtype=dy.dtype, device=dy.device)
+    gemm(dy, wl, dx, M=M, N=K, K=N, trans_b=True, ldb=K, act=act, aux=aux)
+    return dw, db, dx
+
+
+def _mlp_fwd(x1, n2w, n2b, eps, w1, f1b, w2, f2b, rd, rps):
+    """MLP half of a residual block on the f32 stream x1 [M,D]: x1 + drop_path(dropout(fc2(dropout(GELU(fc1(LayerNorm(x1))))))), GELU
+    in fc1's epilogue with the pre-activation kept. w1 [Hd,D], w2 [D,Hd]: the weights in the compute dtype.
+    -> (x2, (mean2, rstd2, ln2, h_pre, h_act) for _mlp_bwd, (hidden mask, fc2 mask))."""
+    M, Hd = x1.shape[0], w1.shape[0]
+    ln2, mean2, rstd2 = layernorm_fwd(x1, n2w, n2b, eps, _compute_dtype)
+    h_pre = torch.empty(M, Hd, dtype=_compute_dtype, device=x1.device)
+    h_act = torch.empty(M, Hd, dtype=_compute_dtype, device=x1.device)
+    gemm(ln2, w1, h_act, M=M, N=Hd, K=x1.shape[1], bias=f1b, act=ACT_GELU, aux=h_pre)
+    mk_h = None
+    if rd is not None and rd.drop > 0:
+        h_act, mk_h = dropout_fwd(h_act, rd, "hidden")
+    x2, mk_2 = _branch_residual(h_act, w2, f2b, x1, rd, 1, rps, "fc2")
+    return x2, (mean2, rstd2, ln2, h_pre, h_act), (mk_h, mk_2)
+
+
+def _mlp_bwd(g2, x1, n2w, saved, w1, w2, prm, nprm, need, rd, rps, masks):
+    """Backward of _mlp_fwd for g2 [M,D] f32, the gradient of x2. prm = (fc1.weight, fc1.bias, fc2.weight, fc2.bias) and nprm =
+    (norm2.weight, norm2.bias), the leaf Parameters that take deferred gradients; need = prm's needs_input_grad flags.
+    -> (g1 f32 at x1, residual path included; its bf16 copy where the LayerNorm backward wrote one; `side`, for the caller's
+    _branch_grad(g1, ...); (dn2w, dn2b, dw1, db1, dw2, db2))."""
+    mean2, rstd2, ln2, h_pre, h_act = saved
+    f1w, f1b, f2w, f2b = prm
+    mk_h, mk_2 = masks
+    T = ln2.dtype
+    bf = T == torch.bfloat16
+    # with the bf16 copy and column-sum partials of the incoming gradient, if the LayerNorm backward that made it (the block
+    # above, when nothing sits in between) left them; bias gradients ride on the weight-gradient launch
+    g2b, g2_lp, g2_cs = _branch_grad(g2, rd, 1, rps, mk_2, T, side=bf)
+    dw2, db2, dh_pre = _linear_bwd(g2_lp, h_act, w2, f2w, f2b, need[2], need[3], dy_f32=g2b, dy_colsum=g2_cs, act=ACT_DGELU, aux=h_pre)
+    if mk_h is not None:            # hidden dropout sits between GELU and fc2: its mask commutes with the GELU' product
+        dh_pre = dropout_bwd(dh_pre, mk_h, rd.drop)
+    dw1, db1, dln2 = _linear_bwd(dh_pre, ln2, w1, f1w, f1b, need[0], need[1])
+    side = bf and rd is None
+    g1, g1_lp, dn2w, dn2b = layernorm_bwd(dln2, x1, n2w, mean2, rstd2, gres=g2, want_lp=side, params=nprm, side=side)
+    return g1, g1_lp, side, (dn2w, dn2b, dw1, db1, dw2, db2)
 
 
 # ----------------------------------------------------------------------------------------------------- patch convolutions
@@ -860,22 +913,13 @@ class ViTBlockFn(torch.autograd.Function):
         else:
             probs, att = attention_fwd(qkv, B, N, heads, dh)
             stat = probs
-        x1, mk_p = _branch_residual(att, wp, pb, x2d, M, D, D, rd, 0, N, "proj")
-        ln2, mean2, rstd2 = layernorm_fwd(x1, n2w, n2b, eps, T)
-        Hd = f1w.shape[0]
-        h_pre = torch.empty(M, Hd, dtype=T, device=dev)
-        h_act = torch.empty(M, Hd, dtype=T, device=dev)
-        gemm(ln2, w1, h_act, M=M, N=Hd, K=D, bias=f1b, act=ACT_GELU, aux=h_pre)
-        mk_h = None
-        if rd is not None and rd.drop > 0:
-            h_act, mk_h = dropout_fwd(h_act, rd, "hidden")
-        x2, mk_2 = _branch_residual(h_act, w2, f2b, x1, M, D, Hd, rd, 1, N, "fc2")
-        ctx.save_for_backward(x2d, n1w, n2w, mean1, rstd1, ln1, qkv, stat, att, x1, mean2, rstd2, ln2, h_pre, h_act,
-                              wq, wp, w1, w2)
-        ctx.dims = (B, N, D, heads, dh, Hd)
+        x1, mk_p = _branch_residual(att, wp, pb, x2d, rd, 0, N, "proj")
+        x2, mlp, mk_mlp = _mlp_fwd(x1, n2w, n2b, eps, w1, f1b, w2, f2b, rd, N)
+        ctx.save_for_backward(x2d, n1w, n2w, mean1, rstd1, ln1, qkv, stat, att, x1, wq, wp, w1, w2, *mlp)
+        ctx.dims = (B, N, D, heads, dh)
         ctx.fused = fused
         ctx.attn_drop = ad_saved
-        ctx.rd, ctx.drop_masks = rd, (mk_p, mk_h, mk_2)
+        ctx.rd, ctx.drop_masks = rd, (mk_p, mk_mlp)
         ctx.prm = (qkvw, qkvb, pw, pb, f1w, f1b, f2w, f2b)     # leaf parameters: targets of the deferred gradients
         ctx.nprm = (n1w, n1b, n2w, n2b)
         out = x2.view(B, N, D)
@@ -887,48 +931,30 @@ class ViTBlockFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g2, *_):
-        (x2d, n1w, n2w, mean1, rstd1, ln1, qkv, stat, att, x1, mean2, rstd2, ln2, h_pre, h_act, wq, wp, w1, w2) = \
-            ctx.saved_tensors
-        B, N, D, heads, dh, Hd = ctx.dims
+        x2d, n1w, n2w, mean1, rstd1, ln1, qkv, stat, att, x1, wq, wp, w1, w2, *mlp = ctx.saved_tensors
+        B, N, D, heads, dh = ctx.dims
         M = B * N
         T = qkv.dtype
-        dev = g2.device
         bf = T == torch.bfloat16
         g2 = _chk(g2.contiguous(), torch.float32).view(M, D)
         rd = ctx.rd
-        mk_p, mk_h, mk_2 = ctx.drop_masks
-        # with the bf16 copy and column-sum partials of the incoming gradient, if the LayerNorm backward that made it left them
-        g2b, g2_lp, g2_cs = _branch_grad(g2, rd, 1, N, mk_2, T, side=bf)
-        qkvw_, qkvb_, pw_, pb_, f1w_, f1b_, f2w_, f2b_ = ctx.prm
+        mk_p, mk_mlp = ctx.drop_masks
+        qkvw_, qkvb_, pw_, pb_ = ctx.prm[:4]
         need = ctx.needs_input_grad
-        # MLP
-        dw2, db2 = _wgrad_bias(g2_lp, h_act, D, Hd, M, f2w_, f2b_, need[11], need[12], dy_f32=g2b, dy_colsum=g2_cs)
-        dh_pre = torch.empty(M, Hd, dtype=T, device=dev)
-        gemm(g2_lp, w2, dh_pre, M=M, N=Hd, K=D, trans_b=True, ldb=Hd, act=ACT_DGELU, aux=h_pre)
-        if mk_h is not None:            # hidden dropout sits between GELU and fc2: its mask commutes with the GELU' product
-            dh_pre = dropout_bwd(dh_pre, mk_h, rd.drop)
-        dw1, db1 = _wgrad_bias(dh_pre, ln2, Hd, D, M, f1w_, f1b_, need[9], need[10])
-        dln2 = torch.empty(M, D, dtype=T, device=dev)
-        gemm(dh_pre, w1, dln2, M=M, N=D, K=Hd, trans_b=True, ldb=D)
-        side = bf and rd is None
-        g1, g1_lp, dn2w, dn2b = layernorm_bwd(dln2, x1, n2w, mean2, rstd2, gres=g2, want_lp=side, params=ctx.nprm[2:], side=side)
+        g1, g1_lp, side, mlp_grads = _mlp_bwd(g2, x1, n2w, mlp, w1, w2, ctx.prm[4:], ctx.nprm[2:], need[9:13], rd, N, mk_mlp)
         g1b, g1_lp, g1_cs = _branch_grad(g1, rd, 0, N, mk_p, T, side=side, lp=g1_lp)
         # attention
-        dwp, dbp = _wgrad_bias(g1_lp, att, D, D, M, pw_, pb_, need[5], need[6], dy_f32=g1b, dy_colsum=g1_cs)
-        datt = torch.empty(M, D, dtype=T, device=dev)
-        gemm(g1_lp, wp, datt, M=M, N=D, K=D, trans_b=True, ldb=D)
+        dwp, dbp, datt = _linear_bwd(g1_lp, att, wp, pw_, pb_, need[5], need[6], dy_f32=g1b, dy_colsum=g1_cs)
         if ctx.attn_drop is not None:
             dqkv = attention_dropout_bwd(qkv, stat, ctx.attn_drop[0], ctx.attn_drop[1], datt, B, N, heads, dh, rd.attn_drop)
         elif ctx.fused:
             dqkv = attention_fused_bwd(qkv, att, datt, stat, B, N, heads, dh)
         else:
             dqkv = attention_bwd(qkv, stat, datt, B, N, heads, dh)
-        dwq, dbq = _wgrad_bias(dqkv, ln1, 3 * D, D, M, qkvw_, qkvb_, need[3], need[4])
-        dln1 = torch.empty(M, D, dtype=T, device=dev)
-        gemm(dqkv, wq, dln1, M=M, N=D, K=3 * D, trans_b=True, ldb=D)
+        dwq, dbq, dln1 = _linear_bwd(dqkv, ln1, wq, qkvw_, qkvb_, need[3], need[4])
         # the block below this one takes g0 as ITS incoming gradient: leave it the bf16 copy and the column sums
         g0, _, dn1w, dn1b = layernorm_bwd(dln1, x2d, n1w, mean1, rstd1, gres=g1, want_lp=bf, params=ctx.nprm[:2], side=bf)
-        return (g0.view(B, N, D), dn1w, dn1b, dwq, dbq, dwp, dbp, dn2w, dn2b, dw1, db1, dw2, db2, None, None, None, None)
+        return (g0.view(B, N, D), dn1w, dn1b, dwq, dbq, dwp, dbp, *mlp_grads, None, None, None, None)
 
 
 class PatchEmbedFn(torch.autograd.Function):
@@ -1416,7 +1442,6 @@ class ConvBlockFn(torch.autograd.Function):
         x2d = _chk(x.detach().contiguous(), torch.float32).view(M, Cc)
         w1, w2, wf1, wf2 = (lp_weight(c1w).view(Cc, Cc), lp_weight(c2w).view(Cc, Cc), lp_weight(f1w).view(-1, Cc),
                             lp_weight(f2w).view(Cc, -1))
-        Hd = wf1.shape[0]
         ln1, mean1, rstd1 = layernorm_fwd(x2d, n1w, n1b, 1e-5, T)
         c1 = torch.empty(M, Cc, dtype=T, device=dev)
         gemm(ln1, w1, c1, M=M, N=Cc, K=Cc, bias=c1b)
@@ -1424,54 +1449,34 @@ class ConvBlockFn(torch.autograd.Function):
         awf = _chk(aw.detach().contiguous(), torch.float32)
         call("evp_dwconv5x5_fwd", ptr(c1), dt(c1), ptr(mask), int(mask_scale), ptr(awf), ptr(ab), B, H, W, Cc, ptr(a), stream_ptr())
         # (CMlp.drop sits after GELU and after fc2, conv_block.py:19-21; the conv branch has no dropout of its own)
-        x1, _ = _branch_residual(a, w2, c2b, x2d, M, Cc, Cc, rd if (rd is None or rd.drop == 0) else BlockDrop(rd.u[0], rd.u[1], rd.keep_prob), 0, HW, "conv2")
-        ln2, mean2, rstd2 = layernorm_fwd(x1, n2w, n2b, 1e-5, T)
-        h_pre = torch.empty(M, Hd, dtype=T, device=dev)
-        h_act = torch.empty(M, Hd, dtype=T, device=dev)
-        gemm(ln2, wf1, h_act, M=M, N=Hd, K=Cc, bias=f1b, act=ACT_GELU, aux=h_pre)
-        mk_h = None
-        if rd is not None and rd.drop > 0:
-            h_act, mk_h = dropout_fwd(h_act, rd, "hidden")
-        x2, mk_2 = _branch_residual(h_act, wf2, f2b, x1, M, Cc, Hd, rd, 1, HW, "fc2")
-        ctx.rd, ctx.drop_masks = rd, (mk_h, mk_2)
-        ctx.save_for_backward(x2d, n1w, n2w, mean1, rstd1, ln1, c1, a, x1, mean2, rstd2, ln2, h_pre, h_act, w1, w2, wf1, wf2, awf, mask)
-        ctx.cfg = (B, H, W, Cc, Hd, int(mask_scale), tuple(aw.shape))
+        x1, _ = _branch_residual(a, w2, c2b, x2d, rd, 0, HW, None)
+        x2, mlp, mk_mlp = _mlp_fwd(x1, n2w, n2b, 1e-5, wf1, f1b, wf2, f2b, rd, HW)
+        ctx.rd, ctx.drop_masks = rd, mk_mlp
+        ctx.save_for_backward(x2d, n1w, n2w, mean1, rstd1, ln1, c1, a, x1, w1, w2, wf1, wf2, awf, mask, *mlp)
+        ctx.cfg = (B, H, W, Cc, int(mask_scale), tuple(aw.shape))
         ctx.prm = (c1w, c1b, c2w, c2b, f1w, f1b, f2w, f2b)
         ctx.nprm = (n1w, n1b, n2w, n2b)
         return x2.view(B, HW, Cc)
 
     @staticmethod
     def backward(ctx, g2):
-        (x2d, n1w, n2w, mean1, rstd1, ln1, c1, a, x1, mean2, rstd2, ln2, h_pre, h_act, w1, w2, wf1, wf2, awf, mask) = ctx.saved_tensors
-        B, H, W, Cc, Hd, mask_scale, awshape = ctx.cfg
-        c1w_, c1b_, c2w_, c2b_, f1w_, f1b_, f2w_, f2b_ = ctx.prm
+        x2d, n1w, n2w, mean1, rstd1, ln1, c1, a, x1, w1, w2, wf1, wf2, awf, mask, *mlp = ctx.saved_tensors
+        B, H, W, Cc, mask_scale, awshape = ctx.cfg
+        c1w_, c1b_, c2w_, c2b_ = ctx.prm[:4]
         need = ctx.needs_input_grad
         M = B * H * W
         T = c1.dtype
         bf = T == torch.bfloat16
         dev = g2.device
         g2 = _chk(g2.contiguous(), torch.float32).view(M, Cc)
+        rd = ctx.rd
+        HW = H * W
         # as in ViTBlockFn: bf16 copy / column sums left by the LayerNorm backward of the block above, bias gradients on the
         # weight-gradient launch, LayerNorm dgamma / dbeta through the grouped column sums
-        rd = ctx.rd
-        mk_h, mk_2 = ctx.drop_masks
-        HW = H * W
-        g2b, g2_lp, g2_cs = _branch_grad(g2, rd, 1, HW, mk_2, T, side=bf)
-        dwf2, db2 = _wgrad_bias(g2_lp, h_act, Cc, Hd, M, f2w_, f2b_, need[13], need[14], dy_f32=g2b, shape=tuple(f2w_.shape), dy_colsum=g2_cs)
-        dh_pre = torch.empty(M, Hd, dtype=T, device=dev)
-        gemm(g2_lp, wf2, dh_pre, M=M, N=Hd, K=Cc, trans_b=True, ldb=Hd, act=ACT_DGELU, aux=h_pre)
-        if mk_h is not None:
-            dh_pre = dropout_bwd(dh_pre, mk_h, rd.drop)
-        dwf1, db1 = _wgrad_bias(dh_pre, ln2, Hd, Cc, M, f1w_, f1b_, need[11], need[12], shape=tuple(f1w_.shape))
-        dln2 = torch.empty(M, Cc, dtype=T, device=dev)
-        gemm(dh_pre, wf1, dln2, M=M, N=Cc, K=Hd, trans_b=True, ldb=Cc)
-        side = bf and rd is None
-        g1, g1_lp, dn2w, dn2b = layernorm_bwd(dln2, x1, n2w, mean2, rstd2, gres=g2, want_lp=side, params=ctx.nprm[2:], side=side)
+        g1, g1_lp, side, mlp_grads = _mlp_bwd(g2, x1, n2w, mlp, wf1, wf2, ctx.prm[4:], ctx.nprm[2:], need[11:15], rd, HW, ctx.drop_masks)
         g1b, g1_lp, g1_cs = _branch_grad(g1, rd, 0, HW, None, T, side=side, lp=g1_lp)
         # conv branch
-        dwc2, dbc2 = _wgrad_bias(g1_lp, a, Cc, Cc, M, c2w_, c2b_, need[7], need[8], dy_f32=g1b, shape=tuple(c2w_.shape), dy_colsum=g1_cs)
-        da = torch.empty(M, Cc, dtype=T, device=dev)
-        gemm(g1_lp, w2, da, M=M, N=Cc, K=Cc, trans_b=True, ldb=Cc)
+        dwc2, dbc2, da = _linear_bwd(g1_lp, a, w2, c2w_, c2b_, need[7], need[8], dy_f32=g1b, dy_colsum=g1_cs)
         dc1 = torch.empty(M, Cc, dtype=T, device=dev)
         daw = torch.empty(Cc, 25, dtype=torch.float32, device=dev)
         dab = torch.empty(Cc, dtype=torch.float32, device=dev)
@@ -1479,12 +1484,9 @@ class ConvBlockFn(torch.autograd.Function):
         ws = torch.empty(ns * 26 * Cc, dtype=torch.float32, device=dev)
         call("evp_dwconv5x5_bwd", ptr(da), ptr(c1), dt(c1), ptr(mask), mask_scale, ptr(awf), B, H, W, Cc, ptr(dc1), ptr(daw), ptr(dab),
              ptr(ws), stream_ptr())
-        dwc1, dbc1 = _wgrad_bias(dc1, ln1, Cc, Cc, M, c1w_, c1b_, need[3], need[4], shape=tuple(c1w_.shape))
-        dln1 = torch.empty(M, Cc, dtype=T, device=dev)
-        gemm(dc1, w1, dln1, M=M, N=Cc, K=Cc, trans_b=True, ldb=Cc)
+        dwc1, dbc1, dln1 = _linear_bwd(dc1, ln1, w1, c1w_, c1b_, need[3], need[4])
         g0, _, dn1w, dn1b = layernorm_bwd(dln1, x2d, n1w, mean1, rstd1, gres=g1, want_lp=bf, params=ctx.nprm[:2], side=bf)
-        return (g0.view(B, H * W, Cc), dn1w, dn1b, dwc1, dbc1, daw.view(awshape), dab, dwc2, dbc2, dn2w, dn2b, dwf1, db1, dwf2, db2,
-                None, None, None, None, None)
+        return (g0.view(B, HW, Cc), dn1w, dn1b, dwc1, dbc1, daw.view(awshape), dab, dwc2, dbc2, *mlp_grads, None, None, None, None, None)
 
 
 def conv_block(x, blk, H, W, mask=None, mask_scale=1, rd=None):
@@ -1613,20 +1615,11 @@ class SwinBlockFn(torch.autograd.Function):
         else:
             call("evp_window_attention_fwd", ptr(qkv), ptr(tab), ptr(_chk(rel, torch.int32)), ptr(att), ptr(probs), Bg, nG, N, heads, R,
                  scale, dt(qkv), ptr(keep), keep_scale, stream_ptr())
-        x1, mk_p = _branch_residual(att, wp, pb, x2d, M, D, D, rd, 0, N, "proj")
-        ln2, mean2, rstd2 = layernorm_fwd(x1, n2w, n2b, eps, T)
-        Hd = f1w.shape[0]
-        h_pre = torch.empty(M, Hd, dtype=T, device=dev)
-        h_act = torch.empty(M, Hd, dtype=T, device=dev)
-        gemm(ln2, w1, h_act, M=M, N=Hd, K=D, bias=f1b, act=ACT_GELU, aux=h_pre)
-        mk_h = None
-        if rd is not None and rd.drop > 0:
-            h_act, mk_h = dropout_fwd(h_act, rd, "hidden")
-        x2, mk_2 = _branch_residual(h_act, w2, f2b, x1, M, D, Hd, rd, 1, N, "fc2")
-        ctx.rd, ctx.drop_masks = rd, (mk_p, mk_h, mk_2)
-        ctx.save_for_backward(x2d, n1w, n2w, mean1, rstd1, ln1, qkv, att, x1, mean2, rstd2, ln2, h_pre, h_act, wq, wp, w1, w2,
-                              tab, rel)
-        ctx.dims = (Bg, nG, N, D, heads, dh, Hd, R, scale)
+        x1, mk_p = _branch_residual(att, wp, pb, x2d, rd, 0, N, "proj")
+        x2, mlp, mk_mlp = _mlp_fwd(x1, n2w, n2b, eps, w1, f1b, w2, f2b, rd, N)
+        ctx.rd, ctx.drop_masks = rd, (mk_p, mk_mlp)
+        ctx.save_for_backward(x2d, n1w, n2w, mean1, rstd1, ln1, qkv, att, x1, wq, wp, w1, w2, tab, rel, *mlp)
+        ctx.dims = (Bg, nG, N, D, heads, R, scale)
         ctx.prm = (qkvw, qkvb, pw, pb, f1w, f1b, f2w, f2b)
         ctx.nprm = (n1w, n1b, n2w, n2b)
         ctx.win = (lse, addm, addmT)          # plain tensors of this node (not inputs / outputs): kept on ctx
@@ -1639,9 +1632,8 @@ class SwinBlockFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g2, *_):
-        (x2d, n1w, n2w, mean1, rstd1, ln1, qkv, att, x1, mean2, rstd2, ln2, h_pre, h_act, wq, wp, w1, w2, tab, rel) = \
-            ctx.saved_tensors
-        Bg, nG, N, D, heads, dh, Hd, R, scale = ctx.dims
+        x2d, n1w, n2w, mean1, rstd1, ln1, qkv, att, x1, wq, wp, w1, w2, tab, rel, *mlp = ctx.saved_tensors
+        Bg, nG, N, D, heads, R, scale = ctx.dims
         M = Bg * N
         T = qkv.dtype
         dev = g2.device
@@ -1650,24 +1642,12 @@ class SwinBlockFn(torch.autograd.Function):
         # as in ViTBlockFn: the LayerNorm backward that produced g2 (the block above, when no regrouping gather sits in between:
         # the single-group stages) may have left its bf16 copy and column sums; bias gradients ride on the weight-gradient launch
         rd = ctx.rd
-        mk_p, mk_h, mk_2 = ctx.drop_masks
-        g2b, g2_lp, g2_cs = _branch_grad(g2, rd, 1, N, mk_2, T, side=bf)
-        qkvw_, qkvb_, pw_, pb_, f1w_, f1b_, f2w_, f2b_ = ctx.prm
+        mk_p, mk_mlp = ctx.drop_masks
+        qkvw_, qkvb_, pw_, pb_ = ctx.prm[:4]
         need = ctx.needs_input_grad
-        dw2, db2 = _wgrad_bias(g2_lp, h_act, D, Hd, M, f2w_, f2b_, need[13], need[14], dy_f32=g2b, dy_colsum=g2_cs)
-        dh_pre = torch.empty(M, Hd, dtype=T, device=dev)
-        gemm(g2_lp, w2, dh_pre, M=M, N=Hd, K=D, trans_b=True, ldb=Hd, act=ACT_DGELU, aux=h_pre)
-        if mk_h is not None:
-            dh_pre = dropout_bwd(dh_pre, mk_h, rd.drop)
-        dw1, db1 = _wgrad_bias(dh_pre, ln2, Hd, D, M, f1w_, f1b_, need[11], need[12])
-        dln2 = torch.empty(M, D, dtype=T, device=dev)
-        gemm(dh_pre, w1, dln2, M=M, N=D, K=Hd, trans_b=True, ldb=D)
-        side = bf and rd is None
-        g1, g1_lp, dn2w, dn2b = layernorm_bwd(dln2, x1, n2w, mean2, rstd2, gres=g2, want_lp=side, params=ctx.nprm[2:], side=side)
+        g1, g1_lp, side, mlp_grads = _mlp_bwd(g2, x1, n2w, mlp, w1, w2, ctx.prm[4:], ctx.nprm[2:], need[11:15], rd, N, mk_mlp)
         g1b, g1_lp, g1_cs = _branch_grad(g1, rd, 0, N, mk_p, T, side=side, lp=g1_lp)
-        dwp, dbp = _wgrad_bias(g1_lp, att, D, D, M, pw_, pb_, need[7], need[8], dy_f32=g1b, dy_colsum=g1_cs)
-        datt = torch.empty(M, D, dtype=T, device=dev)
-        gemm(g1_lp, wp, datt, M=M, N=D, K=D, trans_b=True, ldb=D)
+        dwp, dbp, datt = _linear_bwd(g1_lp, att, wp, pw_, pb_, need[7], need[8], dy_f32=g1b, dy_colsum=g1_cs)
         dqkv = torch.empty(M, 3 * D, dtype=T, device=dev)
         dtable = torch.empty(R, heads, dtype=torch.float32, device=dev)
         lse, addm, addmT = ctx.win
@@ -1680,11 +1660,9 @@ class SwinBlockFn(torch.autograd.Function):
         else:
             call("evp_window_attention_bwd", ptr(qkv), ptr(tab), ptr(rel), ptr(att), ptr(datt), ptr(dqkv), ptr(dtable), Bg, nG, N, heads,
                  R, scale, dt(qkv), ptr(ctx.keep[0]), ctx.keep[1], stream_ptr())
-        dwq, dbq = _wgrad_bias(dqkv, ln1, 3 * D, D, M, qkvw_, qkvb_, need[5], need[6])
-        dln1 = torch.empty(M, D, dtype=T, device=dev)
-        gemm(dqkv, wq, dln1, M=M, N=D, K=3 * D, trans_b=True, ldb=D)
+        dwq, dbq, dln1 = _linear_bwd(dqkv, ln1, wq, qkvw_, qkvb_, need[5], need[6])
         g0, _, dn1w, dn1b = layernorm_bwd(dln1, x2d, n1w, mean1, rstd1, gres=g1, want_lp=bf, params=ctx.nprm[:2], side=bf)
-        return (g0.view(Bg, N, D), dtable, None, dn1w, dn1b, dwq, dbq, dwp, dbp, dn2w, dn2b, dw1, db1, dw2, db2, None, None, None, None)
+        return (g0.view(Bg, N, D), dtable, None, dn1w, dn1b, dwq, dbq, dwp, dbp, *mlp_grads, None, None, None, None)
 
 
 def _attn_keep_mask(rd, shape, dev):
