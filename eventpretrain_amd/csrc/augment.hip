@@ -40,6 +40,62 @@ extern "C" int evp_view_augment_f32(const float *in, const int32_t *params, floa
   return EVP_OK;
 }
 
+// ---- the fine-tuning recipe's view: crop -> BILINEAR resize -> horizontal flip -> time flip ------------------------------
+// evg_augment(mode=args.resize_mode) with the fine-tuning default --resize_mode bilinear (dataset/finetune_cls/
+// ft_n_imagenet_dataset.py:104-106, main_finetune_cls.py:48). F.interpolate(mode='bilinear', align_corners=None) on the cropped view
+// = ATen upsample_bilinear2d, restated in float32 so that the result is EQUAL to the CPU op's, not close to it: per axis
+//   src = max(0, fmaf(in / out, dst + 0.5, -0.5))   one fused multiply-add (an unfused coordinate moves results by up to 1.2e-4)
+//   i0 = min((int)src, in - 1), i1 = i0 + (i0 < in - 1): clamped at the CROP's edge;  l1 = src - i0, l0 = 1 - l1
+// and over the two axes, rows first: top = fmaf(lx0, a, lx1 * b), bot = fmaf(lx0, c, lx1 * d), out = fmaf(ly0, top, ly1 * bot) -- the
+// other sum orders differ from ATen in 20-50 % of the elements by 1-2 ulp. (This is ATen's GENERIC float32 kernel, the one a 5 x 224 x
+// 224 view gets; for Hout + Wout <= 128 the CPU op switches to a channels-last vector kernel with pre-multiplied weights, 1 ulp apart.)
+// HBM-bound like its nearest sibling: x taps and weights once
+// per thread, then the channel loop; the four taps of neighbouring lanes share cache lines, the stores are coalesced.
+// params[b] = {x0, y0, w, h, hflip, tflip}
+__global__ __launch_bounds__(256) void view_augment_bilinear_kernel(const float *__restrict__ in, const int32_t *__restrict__ params,
+                                                                    float *__restrict__ out, int C, int Hin, int Win, int Hout, int Wout,
+                                                                    int negate) {
+  const int b = blockIdx.z, y = blockIdx.y;
+  const int32_t *pr = params + (int64_t)b * 6;
+  const int x0 = pr[0], y0 = pr[1], w = pr[2], h = pr[3], hflip = pr[4], tflip = pr[5];
+  const float sy = (float)h / (float)Hout, sx = (float)w / (float)Wout;
+  const float ry = fmaxf(0.0f, __builtin_fmaf(sy, (float)y + 0.5f, -0.5f));
+  int iy0 = (int)ry;
+  iy0 = iy0 < h - 1 ? iy0 : h - 1;
+  const int iy1 = iy0 + (iy0 < h - 1 ? 1 : 0);
+  const float ly1 = ry - (float)iy0, ly0 = 1.0f - ly1;
+  const int64_t r0 = (int64_t)(y0 + iy0) * Win, r1 = (int64_t)(y0 + iy1) * Win;
+  const float sgn = (tflip && negate) ? -1.0f : 1.0f;
+  for (int x = blockIdx.x * 256 + threadIdx.x; x < Wout; x += gridDim.x * 256) {
+    const int xr = hflip ? Wout - 1 - x : x;          // the flip acts on the resized view
+    const float rx = fmaxf(0.0f, __builtin_fmaf(sx, (float)xr + 0.5f, -0.5f));
+    int ix0 = (int)rx;
+    ix0 = ix0 < w - 1 ? ix0 : w - 1;
+    const int ix1 = ix0 + (ix0 < w - 1 ? 1 : 0);
+    const float lx1 = rx - (float)ix0, lx0 = 1.0f - lx1;
+    const int xa = x0 + ix0, xb = x0 + ix1;
+    for (int c = 0; c < C; ++c) {
+      const int cs = tflip ? C - 1 - c : c;
+      const float *src = in + ((int64_t)b * C + cs) * Hin * Win;
+      const float top = __builtin_fmaf(lx0, src[r0 + xa], lx1 * src[r0 + xb]);
+      const float bot = __builtin_fmaf(lx0, src[r1 + xa], lx1 * src[r1 + xb]);
+      out[(((int64_t)b * C + c) * Hout + y) * Wout + x] = sgn * __builtin_fmaf(ly0, top, ly1 * bot);
+    }
+  }
+}
+
+extern "C" int evp_view_augment_bilinear_f32(const float *in, const int32_t *params, float *out, int B, int C, int Hin, int Win,
+                                             int Hout, int Wout, int negate_on_time_flip, void *stream) {
+  EVP_CHECK_ARG(in && params && out, EVP_EINVAL, "evp_view_augment_bilinear_f32: null pointer");
+  EVP_CHECK_ARG(B > 0 && C > 0 && Hin > 0 && Win > 0 && Hout > 0 && Wout > 0 && B <= 65535 && Hout <= 65535, EVP_ESHAPE,
+                "evp_view_augment_bilinear_f32: bad shape (B=%d C=%d %dx%d -> %dx%d)", B, C, Hin, Win, Hout, Wout);
+  const dim3 grid((unsigned)((Wout + 255) / 256), (unsigned)Hout, (unsigned)B);
+  hipLaunchKernelGGL(view_augment_bilinear_kernel, grid, dim3(256), 0, (hipStream_t)stream, in, params, out, C, Hin, Win, Hout, Wout,
+                     negate_on_time_flip);
+  EVP_CHECK_LAUNCH("evp_view_augment_bilinear_f32");
+  return EVP_OK;
+}
+
 
 // ---- difference-map target: crop -> BICUBIC resize -> horizontal flip -> (negate on time flip) --------------------------
 // dataset/augmentation/view_augment.py:79-89 `frame_augment` (same seed as evg_augment, so the same crop box and flip

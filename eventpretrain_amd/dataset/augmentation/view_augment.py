@@ -1,6 +1,6 @@
 """Voxel-grid view augmentation on the GPU (reference dataset/augmentation/view_augment.py:9-95: `view_crop` ->
-`view_resize(mode='nearest')` -> `view_horizontal_flip` -> `evg_time_flip`), batched: one kernel launch
-(evp_view_augment_f32) for B grids that K1 left in HBM.
+`view_resize(mode='nearest' | 'bilinear')` -> `view_horizontal_flip` -> `evg_time_flip`), batched: one kernel launch
+(evp_view_augment_f32, or evp_view_augment_bilinear_f32 for the fine-tuning recipe's mode) for B grids that K1 left in HBM.
 
 The reference draws its random decisions from the process-global legacy numpy stream inside each DataLoader worker.
 Here they are explicit, host-drawn int32 rows {x0, y0, w, h, hflip, tflip}:
@@ -73,9 +73,16 @@ def evg_uniforms(seed, step, B, first_sample=0):
     return philox_words(seed, step, first_sample + np.arange(B), 4, 10 * 5 + 2).astype(np.float64) * 2.3283064365386963e-10
 
 
-def evg_augment_batch(voxels, params, size, negate=None, out=None):
+VIEW_KERNELS = {"nearest": "evp_view_augment_f32", "bilinear": "evp_view_augment_bilinear_f32"}     # evg_augment's `mode` -> the kernel
+
+
+def evg_augment_batch(voxels, params, size, negate=None, out=None, mode="nearest"):
     """voxels float32 [B,C,H,W] on the GPU, params int32 [B,6] (host array or device tensor) -> float32
-    [B,C,size[0],size[1]]; negate=None applies the reference's rule (5- or 6-bin grids are negated on a time flip)."""
+    [B,C,size[0],size[1]]; negate=None applies the reference's rule (5- or 6-bin grids are negated on a time flip).
+    `mode`: the reference's resize mode -- "nearest" (the pre-training datasets) or "bilinear" (the fine-tuning default,
+    main_finetune_cls.py:48), each equal to F.interpolate on the CPU bit for bit."""
+    if mode not in VIEW_KERNELS:
+        raise ValueError(f"evg_augment_batch: mode must be one of {sorted(VIEW_KERNELS)} (got {mode!r})")
     _lib.require_device()
     if not voxels.is_cuda or voxels.dtype != torch.float32 or not voxels.is_contiguous():
         raise _lib.EvpError("evg_augment_batch: voxels must be a contiguous float32 tensor in device memory")
@@ -92,7 +99,7 @@ def evg_augment_batch(voxels, params, size, negate=None, out=None):
         out = torch.empty(B, C, Ho, Wo, dtype=torch.float32, device=voxels.device)
     if negate is None:
         negate = C in (5, 6)
-    call("evp_view_augment_f32", ptr(voxels), ptr(params), ptr(out), B, C, H, W, Ho, Wo, int(bool(negate)), stream_ptr())
+    call(VIEW_KERNELS[mode], ptr(voxels), ptr(params), ptr(out), B, C, H, W, Ho, Wo, int(bool(negate)), stream_ptr())
     return out
 
 

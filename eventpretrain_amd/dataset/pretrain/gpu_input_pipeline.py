@@ -9,7 +9,8 @@ previous step) and every byte of event / voxel data stays on the device:
 
     window pick + erase / add  csrc/events.hip   evp_events_erase_add_win_f64  (2 launches: sort the <= 1 % added rows in LDS; merge)
     rescale + voxel scatter    csrc/voxel.hip    evp_voxel_scatter_scaled_f32  (K1, 3 launches in the verified mode)
-    crop / resize / flips      csrc/augment.hip  evp_view_augment_f32, evp_frame_augment_f32
+    crop / resize / flips      csrc/augment.hip  evp_view_augment_f32 (nearest) or evp_view_augment_bilinear_f32 (`resize_mode="bilinear"`,
+                                                 the fine-tuning recipe), evp_frame_augment_f32
 
 Decision streams: "device" (default, round 4) = Philox4x32-10 keyed by (seed, step, sample), the per-clip COUNTS, window starts and
 crop boxes computed on the host with array arithmetic (~1 ms per batch) and the erase / add ROWS and noise drawn by a kernel
@@ -55,10 +56,14 @@ class PreparedBatch:
 
 
 class GpuInputPipeline:
-    def __init__(self, args, seed=0, decision_stream="device", ring=4, legacy_order="chain"):
+    def __init__(self, args, seed=0, decision_stream="device", ring=4, legacy_order="chain", resize_mode="nearest"):
         """args: the reference's namespace (fix_events_num, img_sensor_h / _w, input_size, num_bins, crop_min). `ring`: pinned slots
-        for prepared batches (how many may exist at once before their run_prepared)."""
+        for prepared batches (how many may exist at once before their run_prepared). `resize_mode`: evg_augment's `mode`, "nearest"
+        (the pre-training datasets) or "bilinear" (the fine-tuning datasets' default); a keyword of its own, never read from `args`."""
         self.RING = int(ring)
+        if resize_mode not in va.VIEW_KERNELS:
+            raise ValueError(f"resize_mode must be one of {sorted(va.VIEW_KERNELS)} (got {resize_mode!r})")
+        self.resize_mode = resize_mode
         if decision_stream not in ("device", "counter", "legacy"):
             raise ValueError("decision_stream must be 'device', 'counter' or 'legacy'")
         if legacy_order not in ("chain", "n-imagenet"):
@@ -162,7 +167,7 @@ class GpuInputPipeline:
             rows = np.concatenate([rows, fr], 0)
         p_all = torch.from_numpy(rows).to(events.device, non_blocking=True)
         p_dev = p_all[:len(params)]
-        out = va.evg_augment_batch(vox, p_dev, (self.S, self.S))
+        out = va.evg_augment_batch(vox, p_dev, (self.S, self.S), mode=self.resize_mode)
         tgt = None
         if frames is not None:
             fp = p_all[len(params):] if both else (p_dev if frame_params is None else frame_params)
@@ -279,7 +284,7 @@ class GpuInputPipeline:
              ptr(nz_d), ptr(tabs[3]), pb.max_add, float(W), float(H), ptr(ws), ptr(tabs[4]), ptr(ev), stream_ptr())
         vox = voxel_grid_batch(ev, tabs[4], self.bins, (self.S, self.S), assume_sorted=assume_sorted, scale=(self.S / W, self.S / H))
         p_dev = d[o[4]:o[5]].view(torch.int32)[:nc * 6].view(nc, 6)
-        out = va.evg_augment_batch(vox, p_dev, (self.S, self.S))
+        out = va.evg_augment_batch(vox, p_dev, (self.S, self.S), mode=self.resize_mode)
         tgt = None
         if frames is not None:
             fp = d[o[5]:o[6]].view(torch.int32)[:nc * 6].view(nc, 6) if pb.fparams is not None else p_dev
@@ -345,10 +350,13 @@ class GpuInputPipeline:
         """HBM bytes the chain has to move for clips whose picked windows hold `sizes` rows (the figure bench.py prices the chain
         with): read the window (32 B / row) + write the augmented clip (32 B / row; +- 1 %) + K1 reads it again and writes the grid
         once + the view augmentation reads the grid and writes the view. `fused` (CapturedChain's default form): neither the augmented
-        clip nor the raw grid exists -- the window is read once, the augmented view written once."""
+        clip nor the raw grid exists -- the window is read once, the augmented view written once. In bilinear mode the fused K1 stops
+        at the raw grids (see CapturedChain): window read + grid write + grid read + view write."""
         n = float(np.sum(sizes))
         grid = self.bins * self.S * self.S * 4.0 * len(sizes)
-        return (n * 32 + grid) if fused else (n * 32 + n * 32 + n * 32 + grid + grid + grid)
+        if fused:
+            return (n * 32 + grid) if self.resize_mode == "nearest" else (n * 32 + grid + grid + grid)
+        return n * 32 + n * 32 + n * 32 + grid + grid + grid
 
 
 class CapturedChain:
@@ -375,6 +383,11 @@ class CapturedChain:
         self.fused = bool(fused_voxel) and fix <= 48 * 1024 * 8
         self.ev = None if self.fused else torch.zeros(n_clips * (fix + self.kmax), 4, dtype=torch.float64, device=dev)
         self.kws = torch.zeros(n_clips * (pipe.bins + 5), dtype=torch.int64, device=dev) if self.fused else None
+        # bilinear mode: an output row blends two grid rows, and the pair that straddles K1's LDS tile boundary is summed by two
+        # workgroups, so the resize cannot ride on the tile flush -- the fused K1 stops at the raw grids (kept here, static, for whoever
+        # wants to look at them) and evp_view_augment_bilinear_f32 follows on the same stream
+        self.raw = (torch.zeros(n_clips, pipe.bins, pipe.S, pipe.S, dtype=torch.float32, device=dev)
+                    if self.fused and pipe.resize_mode != "nearest" else None)
         self._busy = None
         for t_, shp, who in ((out, (n_clips, pipe.bins, pipe.S, pipe.S), "out"),
                              (tgt_out, None if frames is None else (n_clips, frames.shape[1], pipe.S, pipe.S), "tgt_out")):
@@ -452,16 +465,23 @@ class CapturedChain:
                  float(H), ptr(self.ws), stream_ptr())
             # ... and they leave through the view augmentation (crop / nearest resize / flips), so the raw grids are never stored either
             p_dev = d[o4:o4 + pw].view(torch.int32)[:nc * 6].view(nc, 6)
-            out = self._out_given if self._out_given is not None else torch.empty(nc, pipe.bins, pipe.S, pipe.S, dtype=torch.float32, device=d.device)
-            call("evp_voxel_scatter_fused_f32", ptr(self.events), ptr(tabs[0]), ptr(tabs[1]), nc, ptr(self.er), ptr(tabs[2]), ptr(self.ws),
-                 ptr(tabs[3]), int(pipe.args.fix_events_num), pipe.bins, pipe.S, pipe.S, pipe.S / W, pipe.S / H, ptr(p_dev), pipe.S, pipe.S,
-                 int(pipe.bins in (5, 6)), ptr(self.kws), ptr(out), stream_ptr())
+            if self.raw is None:
+                out = self._out_given if self._out_given is not None else torch.empty(nc, pipe.bins, pipe.S, pipe.S, dtype=torch.float32, device=d.device)
+                call("evp_voxel_scatter_fused_f32", ptr(self.events), ptr(tabs[0]), ptr(tabs[1]), nc, ptr(self.er), ptr(tabs[2]), ptr(self.ws),
+                     ptr(tabs[3]), int(pipe.args.fix_events_num), pipe.bins, pipe.S, pipe.S, pipe.S / W, pipe.S / H, ptr(p_dev), pipe.S, pipe.S,
+                     int(pipe.bins in (5, 6)), ptr(self.kws), ptr(out), stream_ptr())
+            else:
+                # ... or, in bilinear mode, into the chain's own raw grids (no view parameters), which the bilinear view kernel reads
+                call("evp_voxel_scatter_fused_f32", ptr(self.events), ptr(tabs[0]), ptr(tabs[1]), nc, ptr(self.er), ptr(tabs[2]), ptr(self.ws),
+                     ptr(tabs[3]), int(pipe.args.fix_events_num), pipe.bins, pipe.S, pipe.S, pipe.S / W, pipe.S / H, None, 0, 0, 0,
+                     ptr(self.kws), ptr(self.raw), stream_ptr())
+                out = va.evg_augment_batch(self.raw, p_dev, (pipe.S, pipe.S), out=self._out_given, mode=pipe.resize_mode)
         else:
             call("evp_events_erase_add_win_f64", ptr(self.events), ptr(tabs[0]), ptr(tabs[1]), nc, ptr(self.er), ptr(tabs[2]), ptr(self.ai),
                  ptr(self.nz), ptr(tabs[3]), self.kmax, float(W), float(H), ptr(self.ws), ptr(tabs[4]), ptr(self.ev), stream_ptr())
             vox = voxel_grid_batch(self.ev, tabs[4], pipe.bins, (pipe.S, pipe.S), assume_sorted=True, scale=(pipe.S / W, pipe.S / H))
             p_dev = d[o4:o4 + pw].view(torch.int32)[:nc * 6].view(nc, 6)
-            out = va.evg_augment_batch(vox, p_dev, (pipe.S, pipe.S), out=self._out_given)
+            out = va.evg_augment_batch(vox, p_dev, (pipe.S, pipe.S), out=self._out_given, mode=pipe.resize_mode)
         tgt = None
         if fr is not None:
             # (as a parallel branch of the graph the frame targets cost more than they hide: 408 vs 389 us per batch with fork + join)

@@ -492,6 +492,17 @@ int evp_swin_group_windows(const int32_t *counts, int n_windows, int cap, int32_
  * decisions are the caller's: a box with 0 <= x0, x0 + w <= Win, 0 <= y0, y0 + h <= Hin); out float32 [B,C,Hout,Wout]. */
 int evp_view_augment_f32(const float *in, const int32_t *params, float *out, int B, int C, int Hin, int Win, int Hout,
                          int Wout, int negate_on_time_flip, void *stream);
+/* The same chain with the fine-tuning recipe's resize: evg_augment(mode=args.resize_mode) where --resize_mode defaults to 'bilinear'
+ * (main_finetune_cls.py:48; dataset/finetune_cls/ft_n_imagenet_dataset.py:104-106 and its sibling datasets; view_augment.py:35-39
+ * `view_resize` -> utils/reshape.py:40-41 F.interpolate(mode='bilinear', align_corners=None) of the CROPPED view). Same arguments and
+ * params rows as evp_view_augment_f32. The arithmetic is ATen's upsample_bilinear2d in float32, per axis
+ *   src = max(0, fmaf((float)in / (float)out, dst + 0.5f, -0.5f));  i0 = min((int)src, in - 1);  i1 = i0 + (i0 < in - 1);
+ *   l1 = src - i0;  l0 = 1 - l1                                      (taps clamped at the crop's edge, not the image's)
+ * and out = fmaf(ly0, fmaf(lx0, a, lx1 * b), ly1 * fmaf(lx0, c, lx1 * d)) with a, b on the upper row: equal to the CPU op bit for bit
+ * (tests/golden/evg_augment_bilinear.npz) wherever ATen runs its generic float32 kernel -- every view with Hout + Wout > 128; below
+ * that the CPU op takes a vector kernel that is 1 ulp away in about half the elements. A full box at equal size is the identity. */
+int evp_view_augment_bilinear_f32(const float *in, const int32_t *params, float *out, int B, int C, int Hin, int Win, int Hout,
+                                  int Wout, int negate_on_time_flip, void *stream);
 /* Difference-map target of the same sample (reference dataset/augmentation/view_augment.py:79-89 `frame_augment`: view_crop
  * -> view_resize(mode='bicubic') -> view_horizontal_flip -> negate when evg_augment time-flipped): same params rows as
  * evp_view_augment_f32 (the reference re-seeds numpy with the same seed, so crop box and flip coin are the voxel grid's;
