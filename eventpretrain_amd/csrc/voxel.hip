@@ -329,8 +329,9 @@ __global__ __launch_bounds__(512) void voxel_cuts_fused_kernel(const double *eve
 
 // one visit of a row (original or added) by the workgroup of plane b / tile [pix0, pix1); returns false when a verified row is outside
 // `region` (region < -1: no check)
+template <typename CELL>
 __device__ __forceinline__ bool fused_visit(double x, double y, double t, double pd, int W, int64_t pix0, int64_t pix1, double t0, double dT,
-                                            double rT, bool clip_fast, double scale, double bd, double region, float *tile) {
+                                            double rT, bool clip_fast, double scale, double bd, double region, CELL *tile) {
   int64_t pix;
   if (__builtin_fabs(x) < 2147483648.0 && __builtin_fabs(y) < 2147483648.0) pix = (int64_t)(int)x + (int64_t)(int)y * (int64_t)W;
   else pix = (int64_t)x + (int64_t)y * (int64_t)W;
@@ -343,8 +344,8 @@ __device__ __forceinline__ bool fused_visit(double x, double y, double t, double
   float p = (float)pd;
   if (p == 0.0f) p = -1.0f;
   const float dt = (float)(ts - tf);
-  if (tf == bd) atomicAdd(&tile[pix - pix0], p * (1.0f - dt));
-  else if (tf + 1.0 == bd) atomicAdd(&tile[pix - pix0], p * dt);
+  if (tf == bd) atomicAdd(&tile[pix - pix0], (CELL)(p * (1.0f - dt)));
+  else if (tf + 1.0 == bd) atomicAdd(&tile[pix - pix0], (CELL)(p * dt));
   return good;
 }
 
@@ -359,6 +360,11 @@ __device__ __forceinline__ bool erased_beyond_bitmap(const int64_t *er, int64_t 
   return lo < ke && er[lo] == r;
 }
 
+// CELL as in voxel_bin_kernel: float, or double (evp_voxel_scatter_fused_algo_f32's algo 3) -- `ds_add_f64` into a float64 tile, every cell
+// rounded to float32 ONCE at the flush, so the grid no longer depends on the order the LDS atomics arrive in and a launch repeats bit
+// for bit (the noisy validation pass of the fine-tuning loader). The float64 tile holds half the rows: three y-tiles instead of two at
+// 224 x 224, i.e. six instead of four visits per window row.
+template <typename CELL>
 __global__ __launch_bounds__(VB_THREADS) void voxel_bin_fused_kernel(const double *events, const int64_t *win_begin, const int64_t *win_end,
                                                                      const int64_t *erase_idx, const int64_t *erase_off, const double *added,
                                                                      const int64_t *add_off, const int64_t *cuts, const FusedInfo *info, int n_clips,
@@ -366,8 +372,8 @@ __global__ __launch_bounds__(VB_THREADS) void voxel_bin_fused_kernel(const doubl
                                                                      double sx, double sy, float *out, int32_t *flags, const int32_t *view_params,
                                                                      int Hout, int Wout, int negate) {
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-  float *tile = reinterpret_cast<float *>(smem_raw);
-  uint32_t *bm = reinterpret_cast<uint32_t *>(smem_raw + (size_t)tile_rows * W * sizeof(float));     // erased-row bitmap of the window
+  CELL *tile = reinterpret_cast<CELL *>(smem_raw);
+  uint32_t *bm = reinterpret_cast<uint32_t *>(smem_raw + (size_t)tile_rows * W * sizeof(CELL));      // erased-row bitmap of the window
   const int n_j = bins > 1 ? bins - 1 : 1;
   const int per_clip = n_j * n_yt;
   int clip, sub;
@@ -406,7 +412,7 @@ __global__ __launch_bounds__(VB_THREADS) void voxel_bin_fused_kernel(const doubl
     const bool swapped = (j > 0) && ((j & 1) == 0);
     const double bd = (double)b;
     __syncthreads();                       // the bitmap is complete / the previous plane's flush has read the tile
-    for (int i = threadIdx.x; i < tile_elems; i += VB_THREADS) tile[i] = 0.f;
+    for (int i = threadIdx.x; i < tile_elems; i += VB_THREADS) tile[i] = (CELL)0;
     __syncthreads();
     if (n > 0) {
       for (int part = 0; part < (sorted ? 2 : 1); ++part) {
@@ -464,22 +470,26 @@ __global__ __launch_bounds__(VB_THREADS) void voxel_bin_fused_kernel(const doubl
         int ys = (int)floorf((float)y * vsy);
         ys = py0 + (ys < ph - 1 ? ys : ph - 1);
         if (ys < y0 || ys >= y1) continue;
-        const float *src = tile + (ys - y0) * W;
+        const CELL *src = tile + (ys - y0) * W;
         float *dst = plane + (int64_t)y * Wout;
         for (int x = lane; x < Wout; x += 64) {
           const int xr = hflip ? Wout - 1 - x : x;
           int xs = (int)floorf((float)xr * vsx);
           xs = px0 + (xs < pw - 1 ? xs : pw - 1);
-          dst[x] = sgn * src[xs];
+          dst[x] = sgn * (float)src[xs];
         }
       }
     } else {
       float *dst = out + (((int64_t)clip * bins + b) * H + y0) * W;
       if ((W & 3) == 0) {
-        for (int i = threadIdx.x; i < tile_elems / 4; i += VB_THREADS)
-          reinterpret_cast<float4 *>(dst)[i] = reinterpret_cast<const float4 *>(tile)[i];
+        for (int i = threadIdx.x; i < tile_elems / 4; i += VB_THREADS) {
+          if constexpr (std::is_same<CELL, float>::value)
+            reinterpret_cast<float4 *>(dst)[i] = reinterpret_cast<const float4 *>(tile)[i];
+          else
+            reinterpret_cast<float4 *>(dst)[i] = make_float4((float)tile[4 * i], (float)tile[4 * i + 1], (float)tile[4 * i + 2], (float)tile[4 * i + 3]);
+        }
       } else {
-        for (int i = threadIdx.x; i < tile_elems; i += VB_THREADS) dst[i] = tile[i];
+        for (int i = threadIdx.x; i < tile_elems; i += VB_THREADS) dst[i] = (float)tile[i];
       }
     }
   }
@@ -711,25 +721,29 @@ extern "C" int evp_events_sorted_check(const double *events, const int64_t *clip
   return EVP_OK;
 }
 
-extern "C" int evp_voxel_scatter_fused_f32(const double *events, const int64_t *win_begin, const int64_t *win_end, int n_clips,
-                                           const int64_t *erase_idx, const int64_t *erase_offsets, const double *added_rows,
-                                           const int64_t *add_offsets, int64_t max_window, int bins, int H, int W, double scale_x, double scale_y,
-                                           const int32_t *view_params, int view_h, int view_w, int negate_on_time_flip, int64_t *workspace,
-                                           float *out, void *stream) {
+extern "C" int evp_voxel_scatter_fused_algo_f32(const double *events, const int64_t *win_begin, const int64_t *win_end, int n_clips,
+                                                const int64_t *erase_idx, const int64_t *erase_offsets, const double *added_rows,
+                                                const int64_t *add_offsets, int64_t max_window, int bins, int H, int W, double scale_x,
+                                                double scale_y, const int32_t *view_params, int view_h, int view_w, int negate_on_time_flip,
+                                                int64_t *workspace, float *out, int algo, void *stream) {
   EVP_CHECK_ARG(events && win_begin && win_end && erase_idx && erase_offsets && added_rows && add_offsets && workspace && out, EVP_EINVAL,
                 "evp_voxel_scatter_fused_f32: null pointer");
+  EVP_CHECK_ARG(algo == 0 || algo == 3, EVP_EINVAL, "evp_voxel_scatter_fused_f32: algo must be 0 (float32 cells) or 3 (float64 cells), got %d", algo);
   EVP_CHECK_ARG(n_clips > 0 && bins > 0 && bins <= 64 && H > 0 && W > 0 && max_window > 0, EVP_ESHAPE, "evp_voxel_scatter_fused_f32: bad shape");
   EVP_CHECK_ARG(((uintptr_t)events & 15) == 0, EVP_EINVAL, "evp_voxel_scatter_fused_f32: events must be 16-byte aligned");
   EVP_CHECK_ARG(!view_params || (view_h > 0 && view_w > 0), EVP_ESHAPE, "evp_voxel_scatter_fused_f32: view size required with view_params");
   hipStream_t s = (hipStream_t)stream;
+  const bool f64_cells = algo == 3;
+  const size_t cell = f64_cells ? sizeof(double) : sizeof(float);
   const int bm_words = (int)((max_window + 31) / 32);
   const size_t bm_bytes = (size_t)bm_words * 4;
   EVP_CHECK_ARG(bm_bytes <= 48 * 1024, EVP_ESHAPE, "evp_voxel_scatter_fused_f32: windows of at most %d rows (got %lld)", 48 * 1024 * 8, (long long)max_window);
-  const int max_rows = (int)((100 * 1024) / ((size_t)W * sizeof(float)));
+  // f32 cells: <= 100 KiB of tile (as K1); f64 cells: whatever the bitmap leaves of the 160 KiB -- three y-tiles at 224 x 224 and 180 x 240
+  const int max_rows = f64_cells ? (int)((160 * 1024 - bm_bytes) / ((size_t)W * cell)) : (int)((100 * 1024) / ((size_t)W * cell));
   int tile_rows = max_rows < 1 ? 1 : (max_rows > H ? H : max_rows);
   const int n_yt = (H + tile_rows - 1) / tile_rows;
   tile_rows = (H + n_yt - 1) / n_yt;
-  const size_t smem = (size_t)tile_rows * W * sizeof(float) + bm_bytes;
+  const size_t smem = (size_t)tile_rows * W * cell + bm_bytes;
   EVP_CHECK_ARG(smem <= 160 * 1024, EVP_ESHAPE, "evp_voxel_scatter_fused_f32: tile of %d rows x %d + bitmap exceeds LDS", tile_rows, W);
   int64_t *cuts = workspace;
   FusedInfo *info = reinterpret_cast<FusedInfo *>(workspace + (int64_t)n_clips * (bins + 2));
@@ -737,16 +751,26 @@ extern "C" int evp_voxel_scatter_fused_f32(const double *events, const int64_t *
   hipLaunchKernelGGL(voxel_cuts_fused_kernel, dim3(n_clips), dim3(512), 0, s, events, win_begin, win_end, erase_idx, erase_offsets, added_rows, add_offsets, bins,
                      cuts, flags, info);
   EVP_CHECK_LAUNCH("evp_voxel_scatter_fused_f32(cuts)");
+  auto kern = f64_cells ? voxel_bin_fused_kernel<double> : voxel_bin_fused_kernel<float>;
   if (smem > 48 * 1024) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(voxel_bin_fused_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
     EVP_CHECK_ARG(e == hipSuccess, EVP_ELAUNCH, "evp_voxel_scatter_fused_f32: cannot reserve %zu B of LDS: %s", smem, hipGetErrorString(e));
   }
   const int n_blocks = n_clips * (bins > 1 ? bins - 1 : 1) * n_yt;
   for (int pass = 0; pass < 2; ++pass) {
-    hipLaunchKernelGGL(voxel_bin_fused_kernel, dim3(n_blocks), dim3(VB_THREADS), smem, s, events, win_begin, win_end, erase_idx, erase_offsets, added_rows,
+    hipLaunchKernelGGL(kern, dim3(n_blocks), dim3(VB_THREADS), smem, s, events, win_begin, win_end, erase_idx, erase_offsets, added_rows,
                        add_offsets, cuts, info, n_clips, bins, H, W, pass ? 3 : 2, tile_rows, n_yt, bm_words, scale_x, scale_y, out, flags, view_params,
                        view_h, view_w, negate_on_time_flip);
     EVP_CHECK_LAUNCH("evp_voxel_scatter_fused_f32(bin)");
   }
   return EVP_OK;
+}
+
+extern "C" int evp_voxel_scatter_fused_f32(const double *events, const int64_t *win_begin, const int64_t *win_end, int n_clips,
+                                           const int64_t *erase_idx, const int64_t *erase_offsets, const double *added_rows,
+                                           const int64_t *add_offsets, int64_t max_window, int bins, int H, int W, double scale_x, double scale_y,
+                                           const int32_t *view_params, int view_h, int view_w, int negate_on_time_flip, int64_t *workspace,
+                                           float *out, void *stream) {
+  return evp_voxel_scatter_fused_algo_f32(events, win_begin, win_end, n_clips, erase_idx, erase_offsets, added_rows, add_offsets, max_window, bins, H, W,
+                                          scale_x, scale_y, view_params, view_h, view_w, negate_on_time_flip, workspace, out, 0, stream);
 }

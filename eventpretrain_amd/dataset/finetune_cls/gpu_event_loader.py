@@ -8,49 +8,87 @@ happens here per BATCH on the GPU, with the pack / upload machinery of dataset.p
     val     = GpuFinetuneLoader(args, val_samples, batch_size=64, n_batches=len(val_set) // 64, is_train=False, seed=args.seed)
     ft_train_one_epoch(args, model, train, optimizer, epoch, loss_scaler);  ft_val(args, model, val, epoch)
 
+Two recipes, chosen by the caller (`grid`, `sensor`; `finetune_recipe(args)` maps the reference's dataset_type strings to them):
+  grid="input"   N-ImageNet (ft_n_imagenet_dataset.py:79-133): events_reshape sensor -> input_size, voxelise at S x S, crop boxes on S x S;
+                 validation's view_resize of an S x S grid to S x S is the identity in both modes, so no view kernel runs there.
+  grid="sensor"  N-Caltech101, CIFAR10-DVS, DVS128-Gesture, UCF101-DVS, ES-ImageNet with 5 bins (ft_n_caltech101_dataset.py:61-91,
+                 ft_dvs128_gesture_dataset.py:63-89 and siblings): no events_reshape, voxelise at the sensor's (H, W), crop boxes on the
+                 H x W grid, evg_augment (train) / view_resize (val) resizes H x W -> S x S in args.resize_mode.
+
 Train: one replay of the self-driven captured chain (gpu_input_pipeline.CapturedChain) with `resize_mode=args.resize_mode` -- the
 reference's fine-tuning default is 'bilinear' (main_finetune_cls.py:48) -- and windows of args.fix_events_num rows.
 Val: the window pick with args.val_fix_events_num (get_random_index(is_train=False), events_augment.py:9-20; the same rule on word 0 of
-the counter stream), no erase / add, and ONE K1 call with the sensor -> input rescale. No view kernel runs: the reference's
-view_resize of an S x S grid to S x S is the identity in both modes (scale 1: every source coordinate is the pixel's own, weight 1).
+the counter stream), no erase / add, ONE K1 call (with the sensor -> input rescale, or unscaled at the sensor's size) and, where the grid
+is not S x S already, the view kernel under the constant full-box rows -- view_resize alone.
 A validation pass restarts the counter stream at `step0` and bins with K1's float64 cells (algo 3, an order-independent sum), so an
 evaluation set gives the same windows and the same grids, bit for bit, every epoch.
+Noisy val (args.val_event_noise, the reference's robustness evaluation): events_augment's erase / add on the validation window as well,
+then the validation view -- the self-driven captured chain with windows of args.val_fix_events_num rows, no view augmentation and the
+fused K1's float64 cells (evp_voxel_scatter_fused_algo_f32 algo 3), its counter stream reset to (step0, first_sample) at the start of
+every pass: a pass redraws the same erase / add decisions and gives the same bits.
 
 Labels travel with the windows: packed into the pinned slot, uploaded into a per-slot device tensor. They are read by the CONSUMER's
 step, which is queued after this loader yields -- so the event the next upload waits for is recorded on the consumer's stream after
 the generator resumes, behind that step, not behind the chain replay.
 
-Out of scope (NotImplementedError): --val_event_noise (add_noise_events), EvRepSL, the 2- and 3-bin representations."""
+Out of scope (NotImplementedError): EvRepSL, the 2- and 3-bin representations, N-Cars (per-clip grid sizes; see finetune_recipe). The
+reference's add_noise_events (events_augment.py) is called by none of its datasets and is not what --val_event_noise means."""
 import numpy as np
 import torch
 
 from ..dataset_utils.events_to_voxel_grid import voxel_grid_batch
 from ..pretrain.gpu_event_loader import ClipWindowLoader
+from ..augmentation.view_augment import evg_augment_batch
 from ..pretrain.gpu_input_pipeline import GpuInputPipeline
+
+# the reference's dataset_type strings (main_finetune_cls.py) -> (grid, the prefix of its own sensor arguments)
+_RECIPES = {"n-imagenet": ("input", "img"), "n-caltech101": ("sensor", "cal"), "cifar10-dvs": ("sensor", "cifar"),
+            "dvs128_gesture": ("sensor", "gesture"), "ucf101_dvs": ("sensor", "ucf"), "es-imagenet": ("sensor", "esimg")}
+
+
+def finetune_recipe(args):
+    """-> dict(grid=..., sensor=(h, w)): GpuFinetuneLoader's recipe keywords for args.dataset_type, the sensor read from the reference's
+    own argument names for that dataset (cal_sensor_h / _w for N-Caltech101, ...). The loader never calls this on its own."""
+    kind = args.dataset_type
+    if kind == "n-cars":
+        raise NotImplementedError("finetune_recipe: n-cars sizes each grid from the window's own max(x) + 1 and max(y) + 1; that needs per-clip "
+                                  "forms of the plan kernel's crop geometry and of the added-row clipping")
+    if kind not in _RECIPES:
+        raise ValueError(f"finetune_recipe: unknown dataset_type {kind!r} (one of {sorted(_RECIPES)})")
+    grid, prefix = _RECIPES[kind]
+    return dict(grid=grid, sensor=(int(getattr(args, prefix + "_sensor_h")), int(getattr(args, prefix + "_sensor_w"))))
 
 
 class GpuFinetuneLoader(ClipWindowLoader):
-    def __init__(self, args, samples, batch_size, n_batches, is_train, seed=0, first_sample=0, step0=0):
+    def __init__(self, args, samples, batch_size, n_batches, is_train, seed=0, first_sample=0, step0=0, grid="input", sensor=None):
         """`samples`: a re-iterable (one pass per epoch) of (events, label, name); `n_batches`: batches per pass (a short last batch is
         dropped). `step0`: the counter stream's step of the first batch (a training loader continues across epochs, a validation
         loader restarts there). Yields {"events_voxel_grid": float32 [B,bins,S,S], "label": int64 [B], "image_name": [B names]}:
-        device tensors the next batch overwrites."""
+        device tensors the next batch overwrites. `grid` / `sensor`: the recipe (module docstring), passed to GpuInputPipeline."""
         if int(args.num_bins) in (2, 3):
             raise NotImplementedError("GpuFinetuneLoader: the 2- and 3-bin event representations are out of scope (voxel grids only)")
-        if getattr(args, "val_event_noise", False) or getattr(args, "use_evrepsl", False):
-            raise NotImplementedError("GpuFinetuneLoader: --val_event_noise and EvRepSL preprocessing are out of scope")
+        if getattr(args, "use_evrepsl", False):
+            raise NotImplementedError("GpuFinetuneLoader: EvRepSL preprocessing is out of scope")
         self.is_train, self.step0 = bool(is_train), int(step0)
+        self.noisy_val = not self.is_train and bool(getattr(args, "val_event_noise", False))
         fix = int(args.fix_events_num if self.is_train else args.val_fix_events_num)
+        mode = getattr(args, "resize_mode", "bilinear")
+        # (the pipeline validates grid / sensor / mode before any device memory is taken)
+        pipe = GpuInputPipeline(args, seed=seed, resize_mode=mode, grid=grid, sensor=sensor, fix_events_num=fix,
+                                view_augment=self.is_train, voxel_cells="f32" if self.is_train else "f64")
         self._setup(args, samples, batch_size, n_batches, seed, first_sample, step0, fix, fix)
-        self.S, self.bins = int(args.input_size), int(args.num_bins)
-        self.sensor = (int(args.img_sensor_h), int(args.img_sensor_w))
-        self.pipe = self.chain = self.out = None
-        if self.is_train:
-            self.pipe = GpuInputPipeline(args, seed=seed, resize_mode=getattr(args, "resize_mode", "bilinear"))
-            self.chain = self.pipe.capture(self.ev, self.B, clip_offsets=np.zeros(self.B + 1, np.int64))
+        self.S, self.bins, self.resize_mode = int(args.input_size), int(args.num_bins), mode
+        self.sensor, self.grid_hw, self.scale = pipe.sensor, (pipe.gh, pipe.gw), pipe.scale
+        self.pipe = self.chain = self.out = self.raw = None
+        if self.is_train or self.noisy_val:
+            self.pipe = pipe
+            self.chain = pipe.capture(self.ev, self.B, clip_offsets=np.zeros(self.B + 1, np.int64))
             self.d_off = self.chain.d_off
         else:
             self.out = torch.zeros(self.B, self.bins, self.S, self.S, dtype=torch.float32, device=self.dev)
+            if self.grid_hw != (self.S, self.S):          # view_resize is a real resize: K1 into the sensor-sized grids, then the view kernel
+                self.raw = torch.zeros(self.B, self.bins, *self.grid_hw, dtype=torch.float32, device=self.dev)
+                self._full = pipe.full_rows(self.B, self.dev)
 
     def _alloc_extra(self):
         self._lab = [torch.zeros(self.B, dtype=torch.int64, device=self.dev) for _ in range(2)]
@@ -63,20 +101,21 @@ class GpuFinetuneLoader(ClipWindowLoader):
         self._lab[slot].copy_(self._pin_lab[slot], non_blocking=True)
 
     def __iter__(self):
-        H, W = self.sensor
-        if self.is_train:
-            self.chain.set_state(self.step, self.first_sample)
-        else:
+        if not self.is_train:
             self.step = self.step0
+        if self.chain is not None:
+            self.chain.set_state(self.step, self.first_sample)     # (noisy validation: every pass redraws the same erase / add decisions)
         self._mark_read(torch.cuda.current_stream(self.dev))      # (a pass that was left early: its last step is behind this event)
         for b, slot, n, names, cur in self._batches():
-            if self.is_train:
+            if self.chain is not None:
                 vox, _ = self.chain.run_next()
             else:
                 # algo 3: float64 cells in K1's LDS tile -- the sum no longer depends on the order its atomics arrive in, so a pass repeats
                 # bit for bit (the float32 cells of the default differ by an ulp or two from launch to launch); 1.2 x the K1 time
-                vox = voxel_grid_batch(self.ev[:n], self.d_off, self.bins, (self.S, self.S), scale=(self.S / W, self.S / H), out=self.out,
-                                       algo=3)
+                vox = voxel_grid_batch(self.ev[:n], self.d_off, self.bins, self.grid_hw, scale=self.scale,
+                                       out=self.out if self.raw is None else self.raw, algo=3)
+                if self.raw is not None:
+                    vox = evg_augment_batch(vox, self._full, (self.S, self.S), out=self.out, mode=self.resize_mode)
             self.step += 1
             yield {"events_voxel_grid": vox, "label": self._lab[slot], "image_name": names}
             # the consumer has queued its step: what reads the grids, the labels and (before it) the event buffer is on its stream now

@@ -33,7 +33,13 @@ for bit the numpy form above) from a device-resident (step, first sample) pair t
 The captured chain's default voxel stage is FUSED with the event augmentation and the view augmentation
 (evp_voxel_scatter_fused_f32): it streams the original window rows, skips the erased ones, adds the built rows and flushes through
 crop / resize / flips, so neither the merged clip nor the raw grids are ever written (round 4: 449 -> 262 us per 64-clip batch).
-dataset.pretrain.gpu_event_loader.GpuEventLoader puts that chain at the DataLoader's place in the epoch loops."""
+dataset.pretrain.gpu_event_loader.GpuEventLoader puts that chain at the DataLoader's place in the epoch loops.
+
+Recipe keywords (constructor; the defaults are the pre-training chain above): `grid="sensor"` voxelises the UNSCALED events at the
+sensor's (H, W) and lets the view stage resize H x W -> S x S, the crop rows drawn on the H x W grid (five of the reference's
+classification fine-tuning datasets); `sensor`, `fix_events_num` override the namespace's fields; `view_augment=False` makes the view stage
+view_resize alone (the validation recipe); `voxel_cells="f64"` bins the captured chain's fused K1 with float64 LDS cells
+(evp_voxel_scatter_fused_algo_f32, algo 3), whose grids repeat bit for bit from launch to launch."""
 from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
@@ -56,11 +62,25 @@ class PreparedBatch:
 
 
 class GpuInputPipeline:
-    def __init__(self, args, seed=0, decision_stream="device", ring=4, legacy_order="chain", resize_mode="nearest"):
+    def __init__(self, args, seed=0, decision_stream="device", ring=4, legacy_order="chain", resize_mode="nearest", grid="input", sensor=None,
+                 fix_events_num=None, view_augment=True, voxel_cells="f32"):
         """args: the reference's namespace (fix_events_num, img_sensor_h / _w, input_size, num_bins, crop_min). `ring`: pinned slots
         for prepared batches (how many may exist at once before their run_prepared). `resize_mode`: evg_augment's `mode`, "nearest"
-        (the pre-training datasets) or "bilinear" (the fine-tuning datasets' default); a keyword of its own, never read from `args`."""
+        (the pre-training datasets) or "bilinear" (the fine-tuning datasets' default); a keyword of its own, never read from `args`.
+        Neither are the recipe keywords:
+        `grid`: "input" (N-ImageNet: events_reshape to input_size, voxelise at S x S, crop rows drawn on S x S) or "sensor" (N-Caltech101,
+        CIFAR10-DVS, DVS128-Gesture, UCF101-DVS, ES-ImageNet with 5 bins, ft_n_caltech101_dataset.py:61-91: voxelise the unscaled events at
+        the sensor's (H, W), crop rows drawn on H x W, the view stage resizes H x W -> S x S).
+        `sensor`: (h, w) in place of (args.img_sensor_h, args.img_sensor_w). `fix_events_num`: in place of args.fix_events_num (window
+        length, bound of the erase / add counts). `view_augment=False`: the view stage is view_resize alone -- the constant row
+        (0, 0, W, H, 0, 0) for every clip, and no resize at all where the grid already has the view's size (the validation recipe).
+        `voxel_cells`: the captured chain's fused K1 accumulates in "f32" or "f64" LDS cells (evp_voxel_scatter_fused_algo_f32 algo 0 / 3)."""
         self.RING = int(ring)
+        if grid not in ("input", "sensor"):
+            raise ValueError(f"grid must be 'input' or 'sensor' (got {grid!r})")
+        if voxel_cells not in ("f32", "f64"):
+            raise ValueError(f"voxel_cells must be 'f32' or 'f64' (got {voxel_cells!r})")
+        self.grid, self.voxel_cells, self.view_augment = grid, voxel_cells, bool(view_augment)
         if resize_mode not in va.VIEW_KERNELS:
             raise ValueError(f"resize_mode must be one of {sorted(va.VIEW_KERNELS)} (got {resize_mode!r})")
         self.resize_mode = resize_mode
@@ -70,11 +90,34 @@ class GpuInputPipeline:
             raise ValueError("legacy_order must be 'chain' or 'n-imagenet'")
         self.legacy_order = legacy_order
         self.args, self.seed, self.stream = args, int(seed), decision_stream
-        self.sensor = (int(args.img_sensor_h), int(args.img_sensor_w))
+        self.sensor = (int(args.img_sensor_h), int(args.img_sensor_w)) if sensor is None else (int(sensor[0]), int(sensor[1]))
+        self.fix = int(args.fix_events_num if fix_events_num is None else fix_events_num)
         self.S = int(args.input_size)
+        # the grid K1 bins at, and the x / y scale it applies: the input's size after events_reshape, or the sensor's own
+        self.gh, self.gw = (self.S, self.S) if grid == "input" else self.sensor
+        self.scale = (self.S / self.sensor[1], self.S / self.sensor[0]) if grid == "input" else (1.0, 1.0)
+        self._full_rows = {}
         self.bins = int(args.num_bins)
         self.crop_min = float(getattr(args, "crop_min", 0.8))
         self._pins, self._busy, self._turn, self._pool = [None] * self.RING, [None] * self.RING, 0, None
+
+    def full_rows(self, n_clips, device):
+        """The view stage's rows without view augmentation: (0, 0, W, H, 0, 0) per clip, a static device tensor (view_resize alone)."""
+        key = (int(n_clips), str(device))
+        if key not in self._full_rows:
+            self._full_rows[key] = torch.tensor([[0, 0, self.gw, self.gh, 0, 0]] * int(n_clips), dtype=torch.int32, device=device)
+        return self._full_rows[key]
+
+    def _view(self, vox, p_dev, out=None):
+        """Grids [B, bins, gh, gw] -> views [B, bins, S, S]: evg_augment under the drawn rows, or view_resize alone (the identity, and no
+        launch, where the grid has the view's size)."""
+        if not self.view_augment:
+            if (self.gh, self.gw) == (self.S, self.S):
+                if out is None or out.data_ptr() == vox.data_ptr():
+                    return vox
+                return out.copy_(vox)
+            p_dev = self.full_rows(vox.shape[0], vox.device)
+        return va.evg_augment_batch(vox, p_dev, (self.S, self.S), out=out, mode=self.resize_mode)
 
     # ------------------------------------------------------------------------------------------------ host: decisions
     def draw(self, sizes, step, first_sample=0, sample_seeds=None, frame_size=None):
@@ -83,11 +126,11 @@ class GpuInputPipeline:
         sample's seed before frame_augment (pr_ef_imagenet_dataset.py:194-206), so the same uniform draws are scaled to the FRAME's
         size -- the same box only when frame and grid have the same size -- and the time-flip flag is evg_augment's."""
         B = len(sizes)
-        fix = int(self.args.fix_events_num)
+        fix = self.fix
         windows = np.zeros((B, 2), np.int64)
         params = np.zeros((B, 6), np.int32)
         fparams = np.zeros((B, 6), np.int32) if frame_size is not None else None
-        H, W = self.sensor
+        H, W = self.gh, self.gw                                 # the grid the crop boxes are drawn on
         if self.stream == "legacy":
             # one sample after the other, the reference's call order (pr_n_imagenet_dataset.py:83-89 on the running stream; the
             # evg / frame pair re-seeded with np.random.randint(1000) as pr_ef_imagenet_dataset.py:187-195)
@@ -104,11 +147,11 @@ class GpuInputPipeline:
                     windows[i] = (0, n)
                 dec.append(ea.draw_erase_add(int(windows[i, 1] - windows[i, 0])))
                 if self.legacy_order == "n-imagenet":           # evg_augment(args, grid, size): no seed, the stream runs on (:88-89)
-                    params[i] = va.draw_evg_params(np.random, self.S, self.S, self.crop_min)
+                    params[i] = va.draw_evg_params(np.random, H, W, self.crop_min)
                     continue
                 seed2 = np.random.randint(1000)
                 np.random.seed(seed2)                           # evg_augment(..., seed=seed) re-seeds the global stream (view_augment.py:66-67)
-                params[i] = va.draw_evg_params(np.random, self.S, self.S, self.crop_min)
+                params[i] = va.draw_evg_params(np.random, H, W, self.crop_min)
                 if fparams is not None:
                     np.random.seed(seed2)                       # frame_augment(..., seed=seed) does so again (view_augment.py:80-81)
                     fparams[i] = va.draw_evg_params(np.random, int(frame_size[0]), int(frame_size[1]), self.crop_min)
@@ -123,7 +166,7 @@ class GpuInputPipeline:
             # the rows and the noise are drawn on the device: the "decisions" are the two counts per clip
             dec = ea.draw_erase_add_counts(self.seed, step, windows[:, 1] - windows[:, 0], first_sample, words=words)
             U = va.evg_uniforms(self.seed, step, B, first_sample)
-            params = va.draw_evg_params_batch(self.seed, step, B, self.S, self.S, self.crop_min, first_sample, U=U)
+            params = va.draw_evg_params_batch(self.seed, step, B, H, W, self.crop_min, first_sample, U=U)
             if fparams is None:
                 return windows, dec, params
             fparams = va.draw_evg_params_batch(self.seed, step, B, int(frame_size[0]), int(frame_size[1]), self.crop_min, first_sample, U=U)
@@ -137,7 +180,7 @@ class GpuInputPipeline:
             else:
                 windows[i] = (0, n)
         dec = ea.draw_erase_add_batch(self.seed, step, windows[:, 1] - windows[:, 0], first_sample)
-        params = va.draw_evg_params_batch(self.seed, step, B, self.S, self.S, self.crop_min, first_sample)
+        params = va.draw_evg_params_batch(self.seed, step, B, H, W, self.crop_min, first_sample)
         if fparams is None:
             return windows, dec, params
         fparams = va.draw_evg_params_batch(self.seed, step, B, int(frame_size[0]), int(frame_size[1]), self.crop_min, first_sample)
@@ -155,7 +198,7 @@ class GpuInputPipeline:
             raise ValueError("GpuInputPipeline.run takes per-clip decision lists; with decision_stream='device' use prepare() / run_prepared() "
                              "(or batch()), or read the device's draws back with device_decisions()")
         ev, off = ea.events_augment_batch(events, clip_offsets, decisions, (H, W), windows=windows)
-        vox = voxel_grid_batch(ev, off, self.bins, (self.S, self.S), assume_sorted=assume_sorted, scale=(self.S / W, self.S / H))
+        vox = voxel_grid_batch(ev, off, self.bins, (self.gh, self.gw), assume_sorted=assume_sorted, scale=self.scale)
         # the grid's and the frames' parameter rows in ONE upload (each pageable copy is a stall of the host)
         both = frames is not None and frame_params is not None and not torch.is_tensor(frame_params)
         rows = np.ascontiguousarray(params, dtype=np.int32).reshape(-1, 6)
@@ -167,7 +210,7 @@ class GpuInputPipeline:
             rows = np.concatenate([rows, fr], 0)
         p_all = torch.from_numpy(rows).to(events.device, non_blocking=True)
         p_dev = p_all[:len(params)]
-        out = va.evg_augment_batch(vox, p_dev, (self.S, self.S), mode=self.resize_mode)
+        out = self._view(vox, p_dev)
         tgt = None
         if frames is not None:
             fp = p_all[len(params):] if both else (p_dev if frame_params is None else frame_params)
@@ -218,9 +261,8 @@ class GpuInputPipeline:
         if not on_device:
             max_cnt = max_add
         rows = np.ascontiguousarray(params, dtype=np.int32).reshape(n_clips, 6)
-        S = self.S
-        if ((rows[:, 0] < 0) | (rows[:, 1] < 0) | (rows[:, 2] < 1) | (rows[:, 3] < 1) | (rows[:, 0] + rows[:, 2] > S) | (rows[:, 1] + rows[:, 3] > S)).any():
-            raise ValueError("GpuInputPipeline.prepare: crop box outside the view")
+        if ((rows[:, 0] < 0) | (rows[:, 1] < 0) | (rows[:, 2] < 1) | (rows[:, 3] < 1) | (rows[:, 0] + rows[:, 2] > self.gw) | (rows[:, 1] + rows[:, 3] > self.gh)).any():
+            raise ValueError("GpuInputPipeline.prepare: crop box outside the grid")
         n_e, n_a = int(tab[2, -1]), int(tab[3, -1])
         pw = (n_clips * 6 + 1) // 2                      # int32 [B,6] in 8-byte words
         o = [0, n_e, n_e + n_a, n_e + n_a + 3 * n_a, 0, 0, 0] if not on_device else [0, 0, 0, 0, 0, 0, 0]     # (device stream: no decision tables)
@@ -282,9 +324,9 @@ class GpuInputPipeline:
             er_d, ai_d, nz_d = d[o[0]:o[1]], d[o[1]:o[2]], d[o[2]:o[3]]
         call("evp_events_erase_add_win_f64", ptr(events), ptr(tabs[0]), ptr(tabs[1]), nc, ptr(er_d), ptr(tabs[2]), ptr(ai_d),
              ptr(nz_d), ptr(tabs[3]), pb.max_add, float(W), float(H), ptr(ws), ptr(tabs[4]), ptr(ev), stream_ptr())
-        vox = voxel_grid_batch(ev, tabs[4], self.bins, (self.S, self.S), assume_sorted=assume_sorted, scale=(self.S / W, self.S / H))
+        vox = voxel_grid_batch(ev, tabs[4], self.bins, (self.gh, self.gw), assume_sorted=assume_sorted, scale=self.scale)
         p_dev = d[o[4]:o[5]].view(torch.int32)[:nc * 6].view(nc, 6)
-        out = va.evg_augment_batch(vox, p_dev, (self.S, self.S), mode=self.resize_mode)
+        out = self._view(vox, p_dev)
         tgt = None
         if frames is not None:
             fp = d[o[5]:o[6]].view(torch.int32)[:nc * 6].view(nc, 6) if pb.fparams is not None else p_dev
@@ -328,7 +370,7 @@ class GpuInputPipeline:
         first sample) pair that the graph itself advances -- `run_next()` is one replay, with nothing prepared, packed or uploaded on the
         host; `set_clip_offsets` / `set_state` change the inputs between replays.
         `fused_voxel` (default): the voxel grids are binned straight from the window rows, the erase list and the added rows
-        (evp_voxel_scatter_fused_f32) -- the merged clip, which only K1 would read, is never written.
+        (evp_voxel_scatter_fused_algo_f32) -- the merged clip, which only K1 would read, is never written.
         `out` / `tgt_out`: tensors the chain writes its grids [n_clips, bins, S, S] / targets [n_clips, C, S, S] INTO -- the static inputs
         of a step executor, say, which then needs no copy between the two graphs."""
         return CapturedChain(self, events, int(n_clips), frames, clip_offsets, fused_voxel, out, tgt_out)
@@ -351,12 +393,18 @@ class GpuInputPipeline:
         with): read the window (32 B / row) + write the augmented clip (32 B / row; +- 1 %) + K1 reads it again and writes the grid
         once + the view augmentation reads the grid and writes the view. `fused` (CapturedChain's default form): neither the augmented
         clip nor the raw grid exists -- the window is read once, the augmented view written once. In bilinear mode the fused K1 stops
-        at the raw grids (see CapturedChain): window read + grid write + grid read + view write."""
+        at the raw grids (see CapturedChain): window read + grid write + grid read + view write. With
+        grid="sensor" the raw grids have the sensor's size, the views the input's; with view_augment=False and equal sizes no view stage
+        runs."""
         n = float(np.sum(sizes))
-        grid = self.bins * self.S * self.S * 4.0 * len(sizes)
+        grid = self.bins * self.gh * self.gw * 4.0 * len(sizes)           # the raw grids (the sensor's size with grid="sensor")
+        view = self.bins * self.S * self.S * 4.0 * len(sizes)
+        resize = self.view_augment or (self.gh, self.gw) != (self.S, self.S)      # no view kernel where view_resize is the identity
         if fused:
-            return (n * 32 + grid) if self.resize_mode == "nearest" else (n * 32 + grid + grid + grid)
-        return n * 32 + n * 32 + n * 32 + grid + grid + grid
+            if not resize:
+                return n * 32 + view
+            return (n * 32 + view) if self.resize_mode == "nearest" else (n * 32 + grid + grid + view)
+        return n * 32 + n * 32 + n * 32 + grid + ((grid + view) if resize else 0.0)
 
 
 class CapturedChain:
@@ -369,7 +417,7 @@ class CapturedChain:
         _lib.require_device()
         self.pipe, self.events, self.frames, self.nc = pipe, events, frames, n_clips
         dev = events.device
-        fix = int(pipe.args.fix_events_num)
+        fix = self.fix = pipe.fix
         self.kmax = max(int(0.01 * fix), 1)
         pw = (n_clips * 6 + 1) // 2
         # table layout of a device-stream PreparedBatch: five offset rows | crop rows | frame crop rows; two more words: step, first sample
@@ -386,8 +434,11 @@ class CapturedChain:
         # bilinear mode: an output row blends two grid rows, and the pair that straddles K1's LDS tile boundary is summed by two
         # workgroups, so the resize cannot ride on the tile flush -- the fused K1 stops at the raw grids (kept here, static, for whoever
         # wants to look at them) and evp_view_augment_bilinear_f32 follows on the same stream
-        self.raw = (torch.zeros(n_clips, pipe.bins, pipe.S, pipe.S, dtype=torch.float32, device=dev)
-                    if self.fused and pipe.resize_mode != "nearest" else None)
+        # (no view stage at all -- view_augment=False on a grid of the view's size -- needs no raw grids in either mode: K1 writes `out`)
+        self.resize = pipe.view_augment or (pipe.gh, pipe.gw) != (pipe.S, pipe.S)
+        self.raw = (torch.zeros(n_clips, pipe.bins, pipe.gh, pipe.gw, dtype=torch.float32, device=dev)
+                    if self.fused and self.resize and pipe.resize_mode != "nearest" else None)
+        self.algo = 3 if pipe.voxel_cells == "f64" else 0
         self._busy = None
         for t_, shp, who in ((out, (n_clips, pipe.bins, pipe.S, pipe.S), "out"),
                              (tgt_out, None if frames is None else (n_clips, frames.shape[1], pipe.S, pipe.S), "tgt_out")):
@@ -435,7 +486,7 @@ class CapturedChain:
     def _stage(self, pb):
         if pb.n_clips != self.nc or not pb.on_device or pb.n_words != self.n_tab:
             raise ValueError("CapturedChain.run: the prepared batch does not have the captured shape (clips, frames, decision stream)")
-        if pb.max_cnt > self.kmax or int(pb.sizes.max()) > int(self.pipe.args.fix_events_num):
+        if pb.max_cnt > self.kmax or int(pb.sizes.max()) > self.fix:
             raise ValueError("CapturedChain.run: a window or a count exceeds the captured upper bounds")
         h = self.h_tab.numpy()
         h[:self.n_tab] = pb.words.numpy()[:self.n_tab]
@@ -451,8 +502,8 @@ class CapturedChain:
         fr = self.frames
         if self.self_driven:
             # the plan of the batch, on the device: windows, counts and their prefix sums, crop rows; (step, first sample) -> d[n_tab:]
-            call("evp_events_plan_batch", ptr(self.d_off), nc, int(pipe.args.fix_events_num), pipe.seed & (2 ** 64 - 1), ptr(self.state), 1,
-                 ptr(d[self.n_tab:]), pipe.S, pipe.S, 0 if fr is None else int(fr.shape[-2]), 0 if fr is None else int(fr.shape[-1]),
+            call("evp_events_plan_batch", ptr(self.d_off), nc, self.fix, pipe.seed & (2 ** 64 - 1), ptr(self.state), 1,
+                 ptr(d[self.n_tab:]), pipe.gh, pipe.gw, 0 if fr is None else int(fr.shape[-2]), 0 if fr is None else int(fr.shape[-1]),
                  float(pipe.crop_min), ptr(tabs), ptr(d[o4:]), None if fr is None else ptr(d[o4 + pw:]), stream_ptr())
         else:
             d.copy_(self.h_tab, non_blocking=True)        # an upload node of the graph
@@ -464,24 +515,28 @@ class CapturedChain:
             call("evp_events_build_added_f64", ptr(self.events), ptr(tabs[0]), nc, ptr(self.ai), ptr(self.nz), ptr(tabs[3]), self.kmax, float(W),
                  float(H), ptr(self.ws), stream_ptr())
             # ... and they leave through the view augmentation (crop / nearest resize / flips), so the raw grids are never stored either
-            p_dev = d[o4:o4 + pw].view(torch.int32)[:nc * 6].view(nc, 6)
+            p_dev = d[o4:o4 + pw].view(torch.int32)[:nc * 6].view(nc, 6) if pipe.view_augment else pipe.full_rows(nc, d.device)
+            sx, sy = pipe.scale
+            fused_args = (ptr(self.events), ptr(tabs[0]), ptr(tabs[1]), nc, ptr(self.er), ptr(tabs[2]), ptr(self.ws), ptr(tabs[3]), self.fix, pipe.bins,
+                          pipe.gh, pipe.gw, sx, sy)
             if self.raw is None:
                 out = self._out_given if self._out_given is not None else torch.empty(nc, pipe.bins, pipe.S, pipe.S, dtype=torch.float32, device=d.device)
-                call("evp_voxel_scatter_fused_f32", ptr(self.events), ptr(tabs[0]), ptr(tabs[1]), nc, ptr(self.er), ptr(tabs[2]), ptr(self.ws),
-                     ptr(tabs[3]), int(pipe.args.fix_events_num), pipe.bins, pipe.S, pipe.S, pipe.S / W, pipe.S / H, ptr(p_dev), pipe.S, pipe.S,
-                     int(pipe.bins in (5, 6)), ptr(self.kws), ptr(out), stream_ptr())
+                if self.resize:
+                    call("evp_voxel_scatter_fused_algo_f32", *fused_args, ptr(p_dev), pipe.S, pipe.S, int(pipe.bins in (5, 6)), ptr(self.kws), ptr(out),
+                         self.algo, stream_ptr())
+                else:                                     # view_resize of an S x S grid to S x S: the grids are the views
+                    call("evp_voxel_scatter_fused_algo_f32", *fused_args, None, 0, 0, 0, ptr(self.kws), ptr(out), self.algo, stream_ptr())
             else:
                 # ... or, in bilinear mode, into the chain's own raw grids (no view parameters), which the bilinear view kernel reads
-                call("evp_voxel_scatter_fused_f32", ptr(self.events), ptr(tabs[0]), ptr(tabs[1]), nc, ptr(self.er), ptr(tabs[2]), ptr(self.ws),
-                     ptr(tabs[3]), int(pipe.args.fix_events_num), pipe.bins, pipe.S, pipe.S, pipe.S / W, pipe.S / H, None, 0, 0, 0,
-                     ptr(self.kws), ptr(self.raw), stream_ptr())
+                call("evp_voxel_scatter_fused_algo_f32", *fused_args, None, 0, 0, 0, ptr(self.kws), ptr(self.raw), self.algo, stream_ptr())
                 out = va.evg_augment_batch(self.raw, p_dev, (pipe.S, pipe.S), out=self._out_given, mode=pipe.resize_mode)
         else:
             call("evp_events_erase_add_win_f64", ptr(self.events), ptr(tabs[0]), ptr(tabs[1]), nc, ptr(self.er), ptr(tabs[2]), ptr(self.ai),
                  ptr(self.nz), ptr(tabs[3]), self.kmax, float(W), float(H), ptr(self.ws), ptr(tabs[4]), ptr(self.ev), stream_ptr())
-            vox = voxel_grid_batch(self.ev, tabs[4], pipe.bins, (pipe.S, pipe.S), assume_sorted=True, scale=(pipe.S / W, pipe.S / H))
+            vox = voxel_grid_batch(self.ev, tabs[4], pipe.bins, (pipe.gh, pipe.gw), assume_sorted=True, scale=pipe.scale,
+                                   algo=self.algo)
             p_dev = d[o4:o4 + pw].view(torch.int32)[:nc * 6].view(nc, 6)
-            out = va.evg_augment_batch(vox, p_dev, (pipe.S, pipe.S), out=self._out_given, mode=pipe.resize_mode)
+            out = pipe._view(vox, p_dev, out=self._out_given)
         tgt = None
         if fr is not None:
             # (as a parallel branch of the graph the frame targets cost more than they hide: 408 vs 389 us per batch with fork + join)

@@ -31,7 +31,8 @@ enum { EVP_ACT_NONE = 0, EVP_ACT_GELU = 1, EVP_ACT_DGELU = 2, EVP_ACT_RELU = 3, 
 
 const char *evp_last_error(void);
 /* ABI version of this header; bumped on any signature change (2: evp_dropout_fwd takes a device-side seed; evp_gemm_desc lost its
- * stream-K workspace fields in round 3; 3: evp_events_draw_erase_add; 4: keep flags on the window attention; 5: evp_events_plan_batch). A host binding must compare evp_abi_version() with EVP_ABI_VERSION at load time. */
+ * stream-K workspace fields in round 3; 3: evp_events_draw_erase_add; 4: keep flags on the window attention; 5: evp_events_plan_batch; entries ADDED since -- evp_cls_metrics,
+ * evp_view_augment_bilinear_f32, evp_voxel_scatter_fused_algo_f32 -- change no signature and keep 5). A host binding must compare evp_abi_version() with EVP_ABI_VERSION at load time. */
 #define EVP_ABI_VERSION 5
 int evp_abi_version(void);
 /* Name of the code object's target ("gfx950"). */
@@ -139,6 +140,17 @@ int evp_voxel_scatter_fused_f32(const double *events, const int64_t *win_begin, 
                                 const int64_t *add_offsets, int64_t max_window, int bins, int H, int W, double scale_x, double scale_y,
                                 const int32_t *view_params, int view_h, int view_w, int negate_on_time_flip, int64_t *workspace, float *out,
                                 void *stream);
+/* The same with the cell type of the LDS tile as a parameter, numbered as evp_voxel_scatter_f32's algo: 0 = float32 cells (what
+ * evp_voxel_scatter_fused_f32 forwards), 3 = float64 cells (`ds_add_f64`, every cell rounded to float32 once at the flush -- plain or through
+ * the nearest view): the sum does not depend on the order the atomics arrive in, so two launches give the same bits. Any other algo:
+ * EVP_EINVAL. The float64 tile is sized from tile_rows * W * 8 + bitmap <= 160 KiB (three y-tiles at 224 x 224 and 180 x 240 where float32
+ * cells have two). For the fine-tuning datasets' noisy validation (`--val_event_noise`: events_augment on the validation window, then
+ * view_resize; ft_n_caltech101_dataset.py:61-91, ft_n_imagenet_dataset.py:79-133), which must repeat bit for bit from pass to pass. */
+int evp_voxel_scatter_fused_algo_f32(const double *events, const int64_t *win_begin, const int64_t *win_end, int n_clips,
+                                     const int64_t *erase_idx, const int64_t *erase_offsets, const double *added_rows,
+                                     const int64_t *add_offsets, int64_t max_window, int bins, int H, int W, double scale_x, double scale_y,
+                                     const int32_t *view_params, int view_h, int view_w, int negate_on_time_flip, int64_t *workspace, float *out,
+                                     int algo, void *stream);
 
 /* ------------------------------------------------------------------------------------------------ K2 masking
  * Replaces ViT.random_masking, model/backbone/vit.py:91-103 (argsort, argsort, slice, gather) with the noise as an
