@@ -9,6 +9,10 @@
 //                          16-byte stores -- no global atomics, no memset, every output byte written exactly once.
 //      Blocks of one clip are mapped to one XCD (blockIdx % 8) so the slab re-reads (one per plane / y-tile) are
 //      served by that XCD's L2, not by HBM.
+// The FUSED form (voxel_cuts_fused_kernel, voxel_bin_fused_kernel: window rows minus erased rows plus added rows, optionally
+// flushed through the nearest view) is a second composition of the "shared pieces" below, which hold ALL of the per-row
+// arithmetic. The forms differ in where t0 / dT come from (first and last row; min and max over kept and added rows), in which
+// rows are kept (all; erase bitmap in LDS, or bitmap plus erase-list search) and in what the fused one adds (added rows, view).
 // algo 1 keeps the plain global-atomic formulation (memset + 2 atomics per event), algo 2 a decode-once two-pass form
 // (12-byte packed records); both measured slower than the default (5.3x and 1.3x) and stay for A/B measurements.
 //
@@ -38,58 +42,75 @@ __device__ __forceinline__ double stamp(const double *ev, int64_t i, int is_txyp
 // ts exactly as events_to_voxel_grid.py:30/34 computes it (float64): (bins-1) * (t - t0) / dT
 __device__ __forceinline__ double ts_of(double t, double t0, double dT, int bins) { return (double)(bins - 1) * (t - t0) / dT; }
 
-// cuts[c][k], k = 0..bins: first row i (clip-relative) with ts_i >= k; cuts[c][bins+1] = n (unused sentinel)
-// flags (verify mode, else NULL): flags[c] = 1 when the cuts partition the clip the way sorted stamps do (cuts[0] == 0, non-
-// decreasing, cuts[bins] == n) -- the bin kernel then clears it if it meets a row outside the region its position says.
-__global__ __launch_bounds__(512) void voxel_cuts_kernel(const double *events, const int64_t *offsets, int bins, int is_txyp,
-                                                         int64_t *cuts, int32_t *flags) {
-  const int c = blockIdx.x;
-  const int64_t beg = offsets[c], n = offsets[c + 1] - beg;
-  const double *ev = events + beg * 4;
-  int64_t *out = cuts + (int64_t)c * (bins + 2);
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
-  if (n <= 0) {
-    for (int k = threadIdx.x; k <= bins + 1; k += blockDim.x) out[k] = 0;
-    if (flags && threadIdx.x == 0) flags[c] = 1;
-    return;
-  }
-  const double t0 = stamp(ev, 0, is_txyp), t1 = stamp(ev, n - 1, is_txyp);
-  double dT = t1 - t0;
-  if (dT == 0) dT = 1.0;
-  for (int k = wave; k <= bins; k += nw) {
-    int64_t lo = 0, hi = n;  // answer in [lo, hi]
-    while (hi > lo) {
-      const int64_t step = (hi - lo + 63) / 64;
-      const int64_t idx = lo + (int64_t)lane * step;
-      bool pred = false;
-      if (idx < hi) pred = ts_of(stamp(ev, idx, is_txyp), t0, dT, bins) >= (double)k;
-      const unsigned long long m = __ballot(pred);
-      // lanes whose probe is out of range report false; they sit after every in-range probe
-      if (m == 0ull) {
-        const int64_t last = lo + ((hi - 1 - lo) / step) * step;  // last in-range probe
-        lo = last + 1;
-      } else {
-        const int f = __ffsll((long long)m) - 1;
-        const int64_t pf = lo + (int64_t)f * step;
-        if (f > 0) lo = pf - step + 1;
-        hi = pf;
-      }
-    }
-    if (lane == 0) out[k] = lo;
-  }
-  if (threadIdx.x == 0) out[bins + 1] = n;
-  if (flags) {
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      bool ok = out[0] == 0 && out[bins] == n;
-      for (int k = 0; k < bins; ++k) ok = ok && out[k] <= out[k + 1];
-      flags[c] = ok ? 1 : 0;
-    }
-  }
-}
-
 constexpr int VB_THREADS = 1024;
 constexpr int VB_UNROLL = 4;
+
+// ---- shared pieces of the LDS-binned forms (plain and fused) ---------------------------------------------------------------------
+// First row i of the clip (rows ev, n of them, stamps in column col) with ts_i >= k: a 64-ary search by one wave, which all
+// of its lanes return.
+__device__ __forceinline__ int64_t wave_lower_bound(const double *ev, int64_t n, int col, double t0, double dT, int bins, int k) {
+  const int lane = threadIdx.x & 63;
+  int64_t lo = 0, hi = n;  // answer in [lo, hi]
+  while (hi > lo) {
+    const int64_t step = (hi - lo + 63) / 64;
+    const int64_t idx = lo + (int64_t)lane * step;
+    bool pred = false;
+    if (idx < hi) pred = ts_of(ev[idx * 4 + col], t0, dT, bins) >= (double)k;
+    const unsigned long long m = __ballot(pred);
+    // lanes whose probe is out of range report false; they sit after every in-range probe
+    if (m == 0ull) {
+      const int64_t last = lo + ((hi - 1 - lo) / step) * step;  // last in-range probe
+      lo = last + 1;
+    } else {
+      const int f = __ffsll((long long)m) - 1;
+      const int64_t pf = lo + (int64_t)f * step;
+      if (f > 0) lo = pf - step + 1;
+      hi = pf;
+    }
+  }
+  return lo;
+}
+
+// out[k], k = 0..bins: first row i (clip-relative) with ts_i >= k, one wave per k; out[bins+1] = n (unused sentinel). All zero
+// for an empty clip.
+__device__ __forceinline__ void clip_cuts(const double *ev, int64_t n, int col, double t0, double dT, int bins, int64_t *out) {
+  if (n <= 0) {
+    for (int k = threadIdx.x; k <= bins + 1; k += blockDim.x) out[k] = 0;
+    return;
+  }
+  for (int k = threadIdx.x >> 6; k <= bins; k += blockDim.x >> 6) {
+    const int64_t lo = wave_lower_bound(ev, n, col, t0, dT, bins, k);
+    if ((threadIdx.x & 63) == 0) out[k] = lo;
+  }
+  if (threadIdx.x == 0) out[bins + 1] = n;
+}
+
+// Do the cuts partition the clip the way sorted stamps do: non-decreasing, nothing that counts in front of cuts[0] (rows
+// [0, first) do not) or behind cuts[bins] (rows [end, n) do not)? The bin kernel then clears the flag if it meets a row
+// outside the region its position says.
+__device__ __forceinline__ bool cuts_partition(const int64_t *out, int bins, int64_t first, int64_t end) {
+  bool ok = out[0] <= first && out[bins] >= end;
+  for (int k = 0; k < bins; ++k) ok = ok && out[k] <= out[k + 1];
+  return ok;
+}
+
+// the clip's span dT = t1 - t0 as events_to_voxel_grid.py:22-25 takes it (1 where all stamps are equal)
+__device__ __forceinline__ double clip_span(double t0, double t1) {
+  const double dT = t1 - t0;
+  return dT == 0 ? 1.0 : dT;
+}
+
+// workgroup -> (clip, sub), sub = 0 .. per_clip-1: one clip's blocks stay on one XCD (blocks b and b+8 share an XCD)
+__device__ __forceinline__ void block_to_clip(int n_clips, int per_clip, int &clip, int &sub) {
+  if ((n_clips & 7) == 0) {
+    const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
+    clip = (slot / per_clip) * 8 + xcd;
+    sub = slot % per_clip;
+  } else {
+    clip = blockIdx.x / per_clip;
+    sub = blockIdx.x % per_clip;
+  }
+}
 
 // a / d for the clip-constant divisor d, r = RN(1/d): two Newton corrections of q = a*r with exact FMA residuals, the
 // last one is Markstein's final step (q faithful + r correctly rounded => RN(q + (a - q*d)*r) == RN(a/d)), so the
@@ -108,11 +129,6 @@ __device__ __forceinline__ bool in_safe_range(double v) {
   return m >= 0x1p-400 && m <= 0x1p400;  // false for 0, NaN, inf, denormals
 }
 
-// Per event visit: (1) x, y -> flat pixel with 32-bit conversions and the y-tile test, which rejects about half of the
-// visits after ~10 instructions; (2) only for events inside the tile the float64 time normalisation, with the division
-// above. Measured: the kernel is bound by the bytes it pulls through L2 (every event row is visited by ~4 workgroups),
-// not by this arithmetic, so the schedule below is what matters.
-//
 // Schedule. With sorted stamps the clip splits into regions R_k = [cuts[k], cuts[k+1]) (floor(ts) == k); plane b takes
 // the left contributions of R_b and the right contributions of R_(b-1). A clip is served by (bins-1) * n_yt workgroups
 // of EQUAL work (two regions each):
@@ -120,135 +136,197 @@ __device__ __forceinline__ bool in_safe_range(double v) {
 //   j = 1..bins-2: plane j over R_(j-1) then R_j for odd j, R_j then R_(j-1) for even j (rows ascending in both)
 // so that, for odd `bins`, the two planes that need a region stream it during the same half of their lifetime and the
 // second reader finds the rows in the XCD's L2 instead of fetching them again (all blocks of a clip share an XCD).
-// CELL: the accumulator type of the LDS tile: float (default) or double (algo 3, A/B). Round 3 found `ds_add_f32` to serialise its lanes
+__device__ __forceinline__ int jobs_of(int j, int bins) { return (j == 0 && bins > 1) ? 2 : 1; }
+__device__ __forceinline__ int plane_of(int j, int job, int bins) { return job ? bins - 1 : j; }
+
+// What a visit needs: the workgroup's y-tile [y0, y1) of the plane in LDS, the clip's time constants, and the plane / region
+// at hand. CELL: the accumulator type of the LDS tile: float (default) or double (algo 3). Round 3 found `ds_add_f32` to serialise its lanes
 // on gfx950 (3 cycles per lane, 192 per full wave instruction; `ds_add_f64` ~22, `ds_add_u32` ~8 per wave instruction;
-// tools/native/lds_atomic_probe.hip: 197 / 1431 / 2992 G lane-adds/s chip-wide) and SQ_LDS_IDX_ACTIVE at 74 % of this kernel's cycles --
+// tools/native/lds_atomic_probe.hip: 197 / 1431 / 2992 G lane-adds/s chip-wide) and SQ_LDS_IDX_ACTIVE at 74 % of the plain kernel's cycles --
 // yet the atomics are NOT what the kernel waits for: without them it runs 101 -> 93 us, and with f64 cells (three y-tiles instead of two
 // at 224 x 224, i.e. 6 instead of 4 visits per row) 124 us. What it does wait for is the rows themselves: "rows only loaded" is 76 of the
 // 101 us (tools/voxel_parts.py) -- 820 MB through the L1s at 11 TB/s, 70 % of what the eight L2s deliver.
+// With float64 cells (`ds_add_f64`) every cell is rounded to float32 ONCE at the flush, so the grid no longer depends on the order the
+// LDS atomics arrive in and a launch repeats bit for bit (the noisy validation pass of the fine-tuning loader).
+template <typename CELL>
+struct Visit {
+  CELL *tile;
+  int W, y0, y1;
+  int64_t pix0, pix1;           // the tile's flat pixels
+  double sx, sy;                // sensor -> grid rescale of x and y
+  double t0, dT, rT, scale;     // ts = scale * (t - t0) / dT, rT = RN(1 / dT)
+  bool clip_fast;               // dT admits div_by_clip_constant
+  double bd, region;            // the plane; floor(ts) of the slab's rows (see stream_plane)
+  bool check;                   // verified mode: a row outside `region` is reported
+  int dbg;                      // measurement build only
+  __device__ __forceinline__ Visit(CELL *tile_, int yt, int tile_rows, int H, int W_, double sx_, double sy_, double t0_, double dT_, int bins)
+      : tile(tile_), W(W_), y0(yt * tile_rows), y1(y0 + tile_rows < H ? y0 + tile_rows : H), pix0((int64_t)y0 * W_), pix1((int64_t)y1 * W_),
+        sx(sx_), sy(sy_), t0(t0_), dT(dT_), rT(1.0 / dT_), scale((double)(bins - 1)), clip_fast(in_safe_range(dT_)), bd(0.0), region(0.0),
+        check(false), dbg(0) {}
+  __device__ __forceinline__ int elems() const { return (y1 - y0) * W; }
+  __device__ __forceinline__ void clear() const {
+    for (int i = threadIdx.x; i < elems(); i += VB_THREADS) tile[i] = (CELL)0;
+  }
+};
+
+// One visit of a row -- original (x,y,t,p), original (t,x,y,p) when TXYP, or added -- by the workgroup of plane v.bd / tile
+// [pix0, pix1); false when v.check is set and the row is outside v.region. ALL of the per-row arithmetic of both forms:
+// (1) x, y -> flat pixel with 32-bit conversions and the y-tile test, which rejects about half of the visits after ~10
+// instructions; (2) only for events inside the tile the float64 time normalisation, with the division above. Measured: the
+// kernels are bound by the bytes they pull through L2 (every event row is visited by ~4 workgroups), not by this arithmetic.
+// DBG (measurement aid of the plain form, evp_voxel_set_debug; results are garbage when v.dbg is set): 1 = no LDS atomics,
+// 2 = no time normalisation (every row in the tile adds 1), 3 = rows are only loaded. The product instantiations carry no test.
+template <bool TXYP, bool DBG, typename CELL>
+__device__ __forceinline__ bool visit_row(const Visit<CELL> &v, double2 ra, double2 rb) {
+  const double x = (TXYP ? ra.y : ra.x) * v.sx, y = (TXYP ? rb.x : ra.y) * v.sy;
+  const double t = TXYP ? ra.x : rb.x, pd = rb.y;
+  if (DBG && v.dbg == 3) return !(x == 1.2345e300 && pd == t);
+  int64_t pix;
+  if (__builtin_fabs(x) < 2147483648.0 && __builtin_fabs(y) < 2147483648.0)
+    pix = (int64_t)(int)x + (int64_t)(int)y * (int64_t)v.W;  // same truncation as the int64 conversion below
+  else
+    pix = (int64_t)x + (int64_t)y * (int64_t)v.W;
+  if (pix < v.pix0 || pix >= v.pix1) return true;
+  if (DBG && v.dbg == 2) { atomicAdd(&v.tile[pix - v.pix0], (CELL)1); return true; }
+  const double a = v.scale * (t - v.t0);
+  const double ts = (v.clip_fast && in_safe_range(a)) ? div_by_clip_constant(a, v.dT, v.rT) : a / v.dT;
+  const double tf = floor(ts);
+  const bool good = !v.check || tf == v.region;       // NaN is not good
+  if (!(tf >= 0.0)) return good;                      // also rejects NaN
+  float p = (float)pd;
+  if (p == 0.0f) p = -1.0f;
+  const float dt = (float)(ts - tf);
+  float val;
+  if (tf == v.bd) val = p * (1.0f - dt);              // left neighbour, valid since b < bins
+  else if (tf + 1.0 == v.bd) val = p * dt;            // right neighbour
+  else return good;
+  if (DBG && v.dbg == 1) return good && !(val == 1.2345e30f);
+  atomicAdd(&v.tile[pix - v.pix0], (CELL)val);
+  return good;
+}
+
+// The workgroup streams rows [lo, hi) of the clip, 4 per thread in flight (two 16-byte loads each, all issued before the first
+// visit), and visits those for which kept(row) holds; false if a visit was. kept is evaluated for row lo in place of a row
+// behind hi.
+// (Round 3, measured and removed: reading each 64-row block with two fully coalesced instructions -- lane l takes the 16 bytes at
+// 16 l, then at 1024 + 16 l -- and swapping the halves between lane pairs by DPP. Half the cache-line accesses per instruction, yet
+// slower: rows only loaded 84 against 76 us, whole kernel 124 against 101 us; tools/voxel_parts.py.
+// Also: software pipelining with a second batch of 4 rows per thread in flight (unconditional prefetch, so that hipcc's counted
+// waits read vmcnt(14) / (12) / (10) / (8)): 50 against 47 us for 64 workgroups, 105 against 98 us for 512 -- no gain. A workgroup
+// streams its 1.6 MB in ~45 us whether 64 or 256 CUs are busy (tools/voxel_clips_probe.py): ~40 GB/s per CU is what one CU's
+// vector-memory path sustains on rows that mostly miss its L1, and more requests queued behind it do not raise that.)
+template <bool TXYP, bool DBG, typename CELL, typename KEPT>
+__device__ __forceinline__ bool stream_rows(const Visit<CELL> &v, const double *ev, int64_t lo, int64_t hi, KEPT kept) {
+  bool good = true;
+  for (int64_t k0 = threadIdx.x; k0 < hi - lo; k0 += (int64_t)VB_THREADS * VB_UNROLL) {
+    double2 ra[VB_UNROLL], rb[VB_UNROLL];
+    bool live[VB_UNROLL];
+#pragma unroll
+    for (int u = 0; u < VB_UNROLL; ++u) {
+      const int64_t k = k0 + (int64_t)u * VB_THREADS;
+      live[u] = k < hi - lo;
+      const int64_t r = lo + (live[u] ? k : 0);
+      const double *row = ev + r * 4;
+      ra[u] = *reinterpret_cast<const double2 *>(row);
+      rb[u] = *reinterpret_cast<const double2 *>(row + 2);
+      if (!kept(r)) live[u] = false;
+    }
+#pragma unroll
+    for (int u = 0; u < VB_UNROLL; ++u)
+      if (live[u] && !visit_row<TXYP, DBG>(v, ra[u], rb[u])) good = false;
+  }
+  return good;
+}
+
+// The rows of workgroup j's plane b (cc: the clip's cuts, n > 0 rows). sorted: only rows with floor(ts) in {b-1, b} can touch
+// plane b -- two slabs, each walked upward, the upper one first for even j, `region` = floor(ts) of every row of a slab if the
+// stamps are sorted (the last plane's upper slab is the rows with ts == bins - 1); unsorted: the whole clip.
+template <bool TXYP, bool DBG, typename CELL, typename KEPT>
+__device__ __forceinline__ bool stream_plane(Visit<CELL> &v, const double *ev, const int64_t *cc, int64_t n, int j, int b, bool sorted, KEPT kept) {
+  const bool swapped = (j > 0) && ((j & 1) == 0);
+  bool good = true;
+  for (int part = 0; part < (sorted ? 2 : 1); ++part) {
+    const bool upper = (part == 0) == swapped;
+    const int64_t lo = sorted ? (upper ? cc[b] : cc[b > 0 ? b - 1 : 0]) : 0;
+    const int64_t hi = sorted ? (upper ? cc[b + 1] : cc[b]) : n;
+    v.region = upper ? (double)b : (double)b - 1.0;
+    if (!stream_rows<TXYP, DBG>(v, ev, lo, hi, kept)) good = false;
+  }
+  return good;
+}
+
+// the tile -> its rows of the plane at dst: 16-byte stores when W % 4 == 0, every cell rounded to float32 here
+template <typename CELL>
+__device__ __forceinline__ void flush_tile(const CELL *tile, int elems, int W, float *dst) {
+  if ((W & 3) == 0) {
+    for (int i = threadIdx.x; i < elems / 4; i += VB_THREADS) {
+      if constexpr (std::is_same<CELL, float>::value)
+        reinterpret_cast<float4 *>(dst)[i] = reinterpret_cast<const float4 *>(tile)[i];
+      else
+        reinterpret_cast<float4 *>(dst)[i] = make_float4((float)tile[4 * i], (float)tile[4 * i + 1], (float)tile[4 * i + 2], (float)tile[4 * i + 3]);
+    }
+  } else {
+    for (int i = threadIdx.x; i < elems; i += VB_THREADS) dst[i] = (float)tile[i];
+  }
+}
+
+// ---- the plain form ----------------------------------------------------------------------------------------------------------------
+// cuts[c][0 .. bins+1] as clip_cuts writes them, t0 / dT from the clip's first and last row.
+// flags (verify mode, else NULL): flags[c] = cuts_partition of the whole clip.
+__global__ __launch_bounds__(512) void voxel_cuts_kernel(const double *events, const int64_t *offsets, int bins, int is_txyp,
+                                                         int64_t *cuts, int32_t *flags) {
+  const int c = blockIdx.x;
+  const int64_t beg = offsets[c], n = offsets[c + 1] - beg;
+  const double *ev = events + beg * 4;
+  int64_t *out = cuts + (int64_t)c * (bins + 2);
+  const double t0 = n > 0 ? stamp(ev, 0, is_txyp) : 0.0;
+  clip_cuts(ev, n, is_txyp ? 0 : 2, t0, n > 0 ? clip_span(t0, stamp(ev, n - 1, is_txyp)) : 1.0, bins, out);
+  if (flags) {
+    __syncthreads();
+    if (threadIdx.x == 0) flags[c] = cuts_partition(out, bins, 0, n) ? 1 : 0;
+  }
+}
+
+// mode 0: any row order (every block scans its whole clip); 1: sorted stamps promised (slabs between the cuts);
+// 2: as 1, but every row that is normalised is checked to lie in the region its POSITION says (floor(ts) == k for a row
+//    of slab [cuts[k], cuts[k+1])) -- the only property of sortedness the slab schedule uses -- and flags[clip] is
+//    cleared otherwise; 3: repair pass = mode 0 for the clips whose flag is 0, nothing for the others.
+// DBG: the measurement build is a separate instantiation (see visit_row).
 template <bool TXYP, typename CELL, bool DBG>
 __global__ __launch_bounds__(VB_THREADS) void voxel_bin_kernel(const double *events, const int64_t *offsets, const int64_t *cuts,
                                                                int n_clips, int bins, int H, int W, int mode, int tile_rows,
                                                                int n_yt, double sx, double sy, float *out, int32_t *flags, int dbg_arg) {
-  const int dbg = DBG ? dbg_arg : 0;          // the measurement build is a separate instantiation: the product kernel carries no test
-  // dbg (measurement aid, evp_voxel_set_debug; results are garbage when set): 1 = no LDS atomics, 2 = no time normalisation (every row
-  // in the tile adds 1), 3 = rows are only loaded
-  // mode 0: any row order (every block scans its whole clip); 1: sorted stamps promised (slabs between the cuts);
-  // 2: as 1, but every row that is normalised is checked to lie in the region its POSITION says (floor(ts) == k for a row
-  //    of slab [cuts[k], cuts[k+1])) -- the only property of sortedness the slab schedule uses -- and flags[clip] is
-  //    cleared otherwise; 3: repair pass = mode 0 for the clips whose flag is 0, nothing for the others.
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-  CELL *tile = reinterpret_cast<CELL *>(smem_raw);
-  const int n_j = bins > 1 ? bins - 1 : 1;
-  const int per_clip = n_j * n_yt;
   int clip, sub;
-  if ((n_clips & 7) == 0) {  // keep one clip's blocks on one XCD (blocks b and b+8 share an XCD)
-    const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
-    clip = (slot / per_clip) * 8 + xcd;
-    sub = slot % per_clip;
-  } else {
-    clip = blockIdx.x / per_clip;
-    sub = blockIdx.x % per_clip;
-  }
+  block_to_clip(n_clips, (bins > 1 ? bins - 1 : 1) * n_yt, clip, sub);
   if (mode >= 2) {
     const int ok = flags[clip];
     if (mode == 2 ? !ok : ok) return;      // 2: the cuts are no partition, the repair pass takes the clip; 3: nothing to repair
   }
-  const bool assume_sorted = mode == 1 || mode == 2;
+  const bool sorted = mode == 1 || mode == 2;
   bool inconsistent = false;
-  const int j = sub / n_yt, yt = sub % n_yt;
-  const int y0 = yt * tile_rows, y1 = (y0 + tile_rows < H) ? y0 + tile_rows : H;
-  const int tile_elems = (y1 - y0) * W;
-  const int64_t pix0 = (int64_t)y0 * W, pix1 = (int64_t)y1 * W;
+  const int j = sub / n_yt;
   const int64_t beg = offsets[clip], n = offsets[clip + 1] - beg;
   const double *ev = events + beg * 4;
   const int64_t *cc = cuts + (int64_t)clip * (bins + 2);
-  double t0 = 0.0, dT = 1.0;
-  if (n > 0) {
-    t0 = stamp(ev, 0, TXYP);
-    dT = stamp(ev, n - 1, TXYP) - t0;
-    if (dT == 0) dT = 1.0;
-  }
-  const double rT = 1.0 / dT, scale = (double)(bins - 1);
-  const bool clip_fast = in_safe_range(dT);
-
-  const int n_jobs = (j == 0 && bins > 1) ? 2 : 1;
-  for (int job = 0; job < n_jobs; ++job) {
-    const int b = job ? bins - 1 : j;
-    const bool swapped = (j > 0) && ((j & 1) == 0);
-    const double bd = (double)b;
+  const double t0 = n > 0 ? stamp(ev, 0, TXYP) : 0.0;
+  Visit<CELL> v(reinterpret_cast<CELL *>(smem_raw), sub % n_yt, tile_rows, H, W, sx, sy, t0, n > 0 ? clip_span(t0, stamp(ev, n - 1, TXYP)) : 1.0, bins);
+  v.check = mode == 2;
+  v.dbg = DBG ? dbg_arg : 0;
+  for (int job = 0; job < jobs_of(j, bins); ++job) {
+    const int b = plane_of(j, job, bins);
+    v.bd = (double)b;
     if (job) __syncthreads();  // the previous plane's flush has read the tile
-    for (int i = threadIdx.x; i < tile_elems; i += VB_THREADS) tile[i] = (CELL)0;
+    v.clear();
     __syncthreads();
-    if (n > 0) {
-      // sorted: only rows with floor(ts) in {b-1, b} can touch plane b -- two regions, each walked upward, the upper
-      // one first for even j; unsorted: scan the whole clip
-      for (int part = 0; part < (assume_sorted ? 2 : 1); ++part) {
-        const bool upper = (part == 0) == swapped;
-        const int64_t lo = assume_sorted ? (upper ? cc[b] : cc[b > 0 ? b - 1 : 0]) : 0;
-        const int64_t hi = assume_sorted ? (upper ? cc[b + 1] : cc[b]) : n;
-        const double region = upper ? bd : bd - 1.0;      // floor(ts) of every row of this slab if the stamps are sorted
-        // (Round 3, measured and removed: reading each 64-row block with two fully coalesced instructions -- lane l takes the 16 bytes at
-        // 16 l, then at 1024 + 16 l -- and swapping the halves between lane pairs by DPP. Half the cache-line accesses per instruction, yet
-        // slower: rows only loaded 84 against 76 us, whole kernel 124 against 101 us; tools/voxel_parts.py.
-        // Also: software pipelining with a second batch of 4 rows per thread in flight (unconditional prefetch, so that hipcc's counted
-        // waits read vmcnt(14) / (12) / (10) / (8)): 50 against 47 us for 64 workgroups, 105 against 98 us for 512 -- no gain. A workgroup
-        // streams its 1.6 MB in ~45 us whether 64 or 256 CUs are busy (tools/voxel_clips_probe.py): ~40 GB/s per CU is what one CU's
-        // vector-memory path sustains on rows that mostly miss its L1, and more requests queued behind it do not raise that.)
-        for (int64_t k0 = threadIdx.x; k0 < hi - lo; k0 += (int64_t)VB_THREADS * VB_UNROLL) {
-          double2 ra[VB_UNROLL], rb[VB_UNROLL];
-          bool live[VB_UNROLL];
-  #pragma unroll
-          for (int u = 0; u < VB_UNROLL; ++u) {
-            const int64_t k = k0 + (int64_t)u * VB_THREADS;
-            live[u] = k < hi - lo;
-            const double *row = ev + (lo + (live[u] ? k : 0)) * 4;
-            ra[u] = *reinterpret_cast<const double2 *>(row);
-            rb[u] = *reinterpret_cast<const double2 *>(row + 2);
-          }
-  #pragma unroll
-          for (int u = 0; u < VB_UNROLL; ++u) {
-            const double x = (TXYP ? ra[u].y : ra[u].x) * sx, y = (TXYP ? rb[u].x : ra[u].y) * sy;
-            const double t = TXYP ? ra[u].x : rb[u].x, pd = rb[u].y;
-            if (dbg == 3) { if (x == 1.2345e300 && pd == t) inconsistent = true; continue; }
-            int64_t pix;
-            if (__builtin_fabs(x) < 2147483648.0 && __builtin_fabs(y) < 2147483648.0)
-              pix = (int64_t)(int)x + (int64_t)(int)y * (int64_t)W;  // same truncation as the int64 conversion below
-            else
-              pix = (int64_t)x + (int64_t)y * (int64_t)W;
-            if (!live[u] || pix < pix0 || pix >= pix1) continue;
-            if (dbg == 2) { atomicAdd(&tile[pix - pix0], (CELL)1); continue; }
-            const double a = scale * (t - t0);
-            const double ts = (clip_fast && in_safe_range(a)) ? div_by_clip_constant(a, dT, rT) : a / dT;
-            const double tf = floor(ts);
-            if (mode == 2 && !(tf == region)) inconsistent = true;   // NaN included
-            if (!(tf >= 0.0)) continue;                   // also rejects NaN
-            float p = (float)pd;
-            if (p == 0.0f) p = -1.0f;
-            const float dt = (float)(ts - tf);
-            float val;
-            if (tf == bd) val = p * (1.0f - dt);          // left neighbour, valid since b < bins
-            else if (tf + 1.0 == bd) val = p * dt;         // right neighbour
-            else continue;
-            if (dbg == 1) { if (val == 1.2345e30f) inconsistent = true; continue; }
-            atomicAdd(&tile[pix - pix0], (CELL)val);
-          }
-        }
-      }
-    }
+    if (n > 0 && !stream_plane<TXYP, DBG>(v, ev, cc, n, j, b, sorted, [](int64_t) { return true; })) inconsistent = true;
     __syncthreads();
-    float *dst = out + (((int64_t)clip * bins + b) * H + y0) * W;
-    if ((W & 3) == 0) {
-      for (int i = threadIdx.x; i < tile_elems / 4; i += VB_THREADS)
-        reinterpret_cast<float4 *>(dst)[i] = make_float4((float)tile[4 * i], (float)tile[4 * i + 1], (float)tile[4 * i + 2], (float)tile[4 * i + 3]);
-    } else {
-      for (int i = threadIdx.x; i < tile_elems; i += VB_THREADS) dst[i] = (float)tile[i];
-    }
+    flush_tile(v.tile, v.elems(), W, out + (((int64_t)clip * bins + b) * H + v.y0) * W);
   }
   if (inconsistent) flags[clip] = 0;       // every writer stores 0: no atomic needed
 }
 
-// ---- K1 fused with the event-level augmentation of the loader chain --------------------------------------------------------------
+// ---- the fused form: K1 fused with the event-level augmentation of the loader chain ----------------------------------------------
 // The chain's merge kernel writes the augmented clip (window minus the erased rows plus the added rows, time-sorted) only for K1 to
 // read it back four times. The voxel grid does not need that array: it is a SUM over the kept rows, and the only things the order
 // decides are t0 / t1 (first / last stamp of the merged clip). So: the workgroups stream the ORIGINAL window rows through the same
@@ -266,7 +344,6 @@ __global__ __launch_bounds__(512) void voxel_cuts_fused_kernel(const double *eve
   const int64_t beg = win_begin[c], n = win_end[c] - beg;
   const double *ev = events + beg * 4;
   int64_t *out = cuts + (int64_t)c * (bins + 2);
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
   const int64_t e0 = erase_off[c], ke = erase_off[c + 1] - e0, a0 = add_off[c], ka = add_off[c + 1] - a0;
   if (threadIdx.x == 0) {
     const int64_t *E = erase_idx + e0;
@@ -280,73 +357,18 @@ __global__ __launch_bounds__(512) void voxel_cuts_fused_kernel(const double *eve
       const double ta = added[a0 * 4 + 2], tb = added[(a0 + ka - 1) * 4 + 2];
       t0 = have ? fmin(t0, ta) : ta;
       t1 = have ? fmax(t1, tb) : tb;
-      have = true;
     }
-    double dT = t1 - t0;
-    if (dT == 0) dT = 1.0;
-    sh_t0 = t0; sh_dT = dT;
+    sh_t0 = t0; sh_dT = clip_span(t0, t1);
     sh_first = first; sh_last = last;
-    info[c].t0 = t0; info[c].dT = dT;
+    info[c].t0 = t0; info[c].dT = sh_dT;
   }
   __syncthreads();
-  const double t0 = sh_t0, dT = sh_dT;
-  if (n <= 0) {
-    for (int k = threadIdx.x; k <= bins + 1; k += blockDim.x) out[k] = 0;
-    if (threadIdx.x == 0) flags[c] = 1;
-    return;
-  }
-  for (int k = wave; k <= bins; k += nw) {
-    int64_t lo = 0, hi = n;
-    while (hi > lo) {
-      const int64_t step = (hi - lo + 63) / 64;
-      const int64_t idx = lo + (int64_t)lane * step;
-      bool pred = false;
-      if (idx < hi) pred = ts_of(ev[idx * 4 + 2], t0, dT, bins) >= (double)k;
-      const unsigned long long m = __ballot(pred);
-      if (m == 0ull) {
-        const int64_t last = lo + ((hi - 1 - lo) / step) * step;
-        lo = last + 1;
-      } else {
-        const int f = __ffsll((long long)m) - 1;
-        const int64_t pf = lo + (int64_t)f * step;
-        if (f > 0) lo = pf - step + 1;
-        hi = pf;
-      }
-    }
-    if (lane == 0) out[k] = lo;
-  }
-  if (threadIdx.x == 0) out[bins + 1] = n;
+  clip_cuts(ev, n, 2, sh_t0, sh_dT, bins, out);
   __syncthreads();
-  if (threadIdx.x == 0) {
-    // Sorted stamps put nothing but ERASED rows in front of cuts[0] (ts < 0: earlier than the first kept row) and behind cuts[bins]
-    // (later than the last kept one) -- the slabs never visit those two ranges, so a kept row there must send the clip to the repair
-    // pass; between them the bin kernel checks every kept row it normalises.
-    bool ok = out[0] <= sh_first && out[bins] >= sh_last + 1;
-    for (int k = 0; k < bins; ++k) ok = ok && out[k] <= out[k + 1];
-    flags[c] = ok ? 1 : 0;
-  }
-}
-
-// one visit of a row (original or added) by the workgroup of plane b / tile [pix0, pix1); returns false when a verified row is outside
-// `region` (region < -1: no check)
-template <typename CELL>
-__device__ __forceinline__ bool fused_visit(double x, double y, double t, double pd, int W, int64_t pix0, int64_t pix1, double t0, double dT,
-                                            double rT, bool clip_fast, double scale, double bd, double region, CELL *tile) {
-  int64_t pix;
-  if (__builtin_fabs(x) < 2147483648.0 && __builtin_fabs(y) < 2147483648.0) pix = (int64_t)(int)x + (int64_t)(int)y * (int64_t)W;
-  else pix = (int64_t)x + (int64_t)y * (int64_t)W;
-  if (pix < pix0 || pix >= pix1) return true;
-  const double a = scale * (t - t0);
-  const double ts = (clip_fast && in_safe_range(a)) ? div_by_clip_constant(a, dT, rT) : a / dT;
-  const double tf = floor(ts);
-  const bool good = region < -1.5 || tf == region;
-  if (!(tf >= 0.0)) return good;
-  float p = (float)pd;
-  if (p == 0.0f) p = -1.0f;
-  const float dt = (float)(ts - tf);
-  if (tf == bd) atomicAdd(&tile[pix - pix0], (CELL)(p * (1.0f - dt)));
-  else if (tf + 1.0 == bd) atomicAdd(&tile[pix - pix0], (CELL)(p * dt));
-  return good;
+  // Sorted stamps put nothing but ERASED rows in front of cuts[0] (ts < 0: earlier than the first kept row) and behind cuts[bins]
+  // (later than the last kept one) -- the slabs never visit those two ranges, so a kept row there must send the clip to the repair
+  // pass; between them the bin kernel checks every kept row it normalises.
+  if (threadIdx.x == 0) flags[c] = (n <= 0 || cuts_partition(out, bins, sh_first, sh_last + 1)) ? 1 : 0;
 }
 
 // a window row behind the bitmap (window longer than max_window): binary search in the ascending erase list
@@ -360,10 +382,8 @@ __device__ __forceinline__ bool erased_beyond_bitmap(const int64_t *er, int64_t 
   return lo < ke && er[lo] == r;
 }
 
-// CELL as in voxel_bin_kernel: float, or double (evp_voxel_scatter_fused_algo_f32's algo 3) -- `ds_add_f64` into a float64 tile, every cell
-// rounded to float32 ONCE at the flush, so the grid no longer depends on the order the LDS atomics arrive in and a launch repeats bit
-// for bit (the noisy validation pass of the fine-tuning loader). The float64 tile holds half the rows: three y-tiles instead of two at
-// 224 x 224, i.e. six instead of four visits per window row.
+// mode 2: fast pass for the clips whose cuts are a partition; 3: repair pass (whole-clip scan) for the others.
+// The float64 tile holds half the rows: three y-tiles instead of two at 224 x 224, i.e. six instead of four visits per window row.
 template <typename CELL>
 __global__ __launch_bounds__(VB_THREADS) void voxel_bin_fused_kernel(const double *events, const int64_t *win_begin, const int64_t *win_end,
                                                                      const int64_t *erase_idx, const int64_t *erase_off, const double *added,
@@ -372,33 +392,18 @@ __global__ __launch_bounds__(VB_THREADS) void voxel_bin_fused_kernel(const doubl
                                                                      double sx, double sy, float *out, int32_t *flags, const int32_t *view_params,
                                                                      int Hout, int Wout, int negate) {
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-  CELL *tile = reinterpret_cast<CELL *>(smem_raw);
   uint32_t *bm = reinterpret_cast<uint32_t *>(smem_raw + (size_t)tile_rows * W * sizeof(CELL));      // erased-row bitmap of the window
-  const int n_j = bins > 1 ? bins - 1 : 1;
-  const int per_clip = n_j * n_yt;
   int clip, sub;
-  if ((n_clips & 7) == 0) {
-    const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
-    clip = (slot / per_clip) * 8 + xcd;
-    sub = slot % per_clip;
-  } else {
-    clip = blockIdx.x / per_clip;
-    sub = blockIdx.x % per_clip;
-  }
+  block_to_clip(n_clips, (bins > 1 ? bins - 1 : 1) * n_yt, clip, sub);
   const int ok = flags[clip];
-  if (mode == 2 ? !ok : ok) return;        // 2: fast pass for the clips whose cuts are a partition; 3: repair pass for the others
+  if (mode == 2 ? !ok : ok) return;
   const bool sorted = mode == 2;
   bool inconsistent = false;
-  const int j = sub / n_yt, yt = sub % n_yt;
-  const int y0 = yt * tile_rows, y1 = (y0 + tile_rows < H) ? y0 + tile_rows : H;
-  const int tile_elems = (y1 - y0) * W;
-  const int64_t pix0 = (int64_t)y0 * W, pix1 = (int64_t)y1 * W;
+  const int j = sub / n_yt;
   const int64_t beg = win_begin[clip], n = win_end[clip] - beg;
   const double *ev = events + beg * 4;
   const int64_t *cc = cuts + (int64_t)clip * (bins + 2);
-  const double t0 = info[clip].t0, dT = info[clip].dT;
-  const double rT = 1.0 / dT, scale = (double)(bins - 1);
-  const bool clip_fast = in_safe_range(dT);
+  Visit<CELL> v(reinterpret_cast<CELL *>(smem_raw), sub % n_yt, tile_rows, H, W, sx, sy, info[clip].t0, info[clip].dT, bins);
   const int64_t e0 = erase_off[clip], ke = erase_off[clip + 1] - e0, a0 = add_off[clip], ka = add_off[clip + 1] - a0;
   for (int i = threadIdx.x; i < bm_words; i += VB_THREADS) bm[i] = 0u;
   __syncthreads();
@@ -406,54 +411,25 @@ __global__ __launch_bounds__(VB_THREADS) void voxel_bin_fused_kernel(const doubl
     const int64_t r = erase_idx[e0 + q];
     if (r >= 0 && r < n && (r >> 5) < bm_words) atomicOr(&bm[r >> 5], 1u << (r & 31));
   }
-  const int n_jobs = (j == 0 && bins > 1) ? 2 : 1;
-  for (int job = 0; job < n_jobs; ++job) {
-    const int b = job ? bins - 1 : j;
-    const bool swapped = (j > 0) && ((j & 1) == 0);
-    const double bd = (double)b;
+  // a window longer than the bitmap (max_window too small) looks its rows behind the bitmap up in the erase list; the choice is
+  // per workgroup, so a window that fits runs the bitmap-only loop (the lookup inside it cost 3 % of the chain: 264 vs 256 us)
+  const auto kept_bitmap = [&](int64_t r) { return ((bm[r >> 5] >> (r & 31)) & 1u) == 0u; };
+  const auto kept_beyond = [&](int64_t r) { return (r >> 5) >= bm_words ? !erased_beyond_bitmap(erase_idx + e0, ke, r) : kept_bitmap(r); };
+  for (int job = 0; job < jobs_of(j, bins); ++job) {
+    const int b = plane_of(j, job, bins);
+    v.bd = (double)b;
     __syncthreads();                       // the bitmap is complete / the previous plane's flush has read the tile
-    for (int i = threadIdx.x; i < tile_elems; i += VB_THREADS) tile[i] = (CELL)0;
+    v.clear();
     __syncthreads();
-    if (n > 0) {
-      for (int part = 0; part < (sorted ? 2 : 1); ++part) {
-        const bool upper = (part == 0) == swapped;
-        const int64_t lo = sorted ? (upper ? cc[b] : cc[b > 0 ? b - 1 : 0]) : 0;
-        // the last plane also takes what lies behind cuts[bins]: kept rows with ts == bins - 1 sit in front of it, rows behind it are erased
-        const int64_t hi = sorted ? (upper ? cc[b + 1] : cc[b]) : n;
-        const double region = sorted ? (upper ? bd : bd - 1.0) : -2.0;
-        // a window longer than the bitmap (max_window too small) looks its rows behind the bitmap up in the erase list; the choice is
-        // per workgroup, so a window that fits runs the bitmap-only loop (the lookup inside it cost 3 % of the chain: 264 vs 256 us)
-        auto stream = [&](auto beyond) {
-          for (int64_t k0 = threadIdx.x; k0 < hi - lo; k0 += (int64_t)VB_THREADS * VB_UNROLL) {
-            double2 ra[VB_UNROLL], rb[VB_UNROLL];
-            bool live[VB_UNROLL];
-#pragma unroll
-            for (int u = 0; u < VB_UNROLL; ++u) {
-              const int64_t k = k0 + (int64_t)u * VB_THREADS;
-              live[u] = k < hi - lo;
-              const int64_t r = lo + (live[u] ? k : 0);
-              const double *row = ev + r * 4;
-              ra[u] = *reinterpret_cast<const double2 *>(row);
-              rb[u] = *reinterpret_cast<const double2 *>(row + 2);
-              const bool erased = (decltype(beyond)::value && (r >> 5) >= bm_words) ? erased_beyond_bitmap(erase_idx + e0, ke, r)
-                                                                                    : ((bm[r >> 5] >> (r & 31)) & 1u) != 0u;
-              if (live[u] && erased) live[u] = false;
-            }
-#pragma unroll
-            for (int u = 0; u < VB_UNROLL; ++u) {
-              if (!live[u]) continue;
-              if (!fused_visit(ra[u].x * sx, ra[u].y * sy, rb[u].x, rb[u].y, W, pix0, pix1, t0, dT, rT, clip_fast, scale, bd, region, tile)) inconsistent = true;
-            }
-          }
-        };
-        if (n <= (int64_t)bm_words * 32) stream(std::false_type{});
-        else stream(std::true_type{});
-      }
-    }
+    v.check = sorted;                      // (rows behind cuts[bins], which no slab visits, are erased)
+    if (n > 0 && !(n <= (int64_t)bm_words * 32 ? stream_plane<false, false>(v, ev, cc, n, j, b, sorted, kept_bitmap)
+                                               : stream_plane<false, false>(v, ev, cc, n, j, b, sorted, kept_beyond)))
+      inconsistent = true;
     // the added rows (built, clipped to the sensor and time-sorted by build_added_kernel): every workgroup of the clip looks at all of them
+    v.check = false;
     for (int64_t q = threadIdx.x; q < ka; q += VB_THREADS) {
       const double *row = added + (a0 + q) * 4;
-      fused_visit(row[0] * sx, row[1] * sy, row[2], row[3], W, pix0, pix1, t0, dT, rT, clip_fast, scale, bd, -2.0, tile);
+      visit_row<false, false>(v, make_double2(row[0], row[1]), make_double2(row[2], row[3]));
     }
     __syncthreads();
     if (view_params) {
@@ -469,8 +445,8 @@ __global__ __launch_bounds__(VB_THREADS) void voxel_bin_fused_kernel(const doubl
       for (int y = wave; y < Hout; y += VB_THREADS / 64) {          // a wave per output row: the row test is wave-uniform
         int ys = (int)floorf((float)y * vsy);
         ys = py0 + (ys < ph - 1 ? ys : ph - 1);
-        if (ys < y0 || ys >= y1) continue;
-        const CELL *src = tile + (ys - y0) * W;
+        if (ys < v.y0 || ys >= v.y1) continue;
+        const CELL *src = v.tile + (ys - v.y0) * W;
         float *dst = plane + (int64_t)y * Wout;
         for (int x = lane; x < Wout; x += 64) {
           const int xr = hflip ? Wout - 1 - x : x;
@@ -480,17 +456,7 @@ __global__ __launch_bounds__(VB_THREADS) void voxel_bin_fused_kernel(const doubl
         }
       }
     } else {
-      float *dst = out + (((int64_t)clip * bins + b) * H + y0) * W;
-      if ((W & 3) == 0) {
-        for (int i = threadIdx.x; i < tile_elems / 4; i += VB_THREADS) {
-          if constexpr (std::is_same<CELL, float>::value)
-            reinterpret_cast<float4 *>(dst)[i] = reinterpret_cast<const float4 *>(tile)[i];
-          else
-            reinterpret_cast<float4 *>(dst)[i] = make_float4((float)tile[4 * i], (float)tile[4 * i + 1], (float)tile[4 * i + 2], (float)tile[4 * i + 3]);
-        }
-      } else {
-        for (int i = threadIdx.x; i < tile_elems; i += VB_THREADS) dst[i] = (float)tile[i];
-      }
+      flush_tile(v.tile, v.elems(), W, out + (((int64_t)clip * bins + b) * H + v.y0) * W);
     }
   }
   if (inconsistent) flags[clip] = 0;
@@ -533,16 +499,8 @@ __global__ __launch_bounds__(VB_THREADS) void voxel_bin_packed_kernel(const uint
                                                                       int H, int W, int assume_sorted, int tile_rows, int n_yt, float *out) {
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
   float *tile = reinterpret_cast<float *>(smem_raw);
-  const int per_clip = bins * n_yt;
   int clip, sub;
-  if ((n_clips & 7) == 0) {
-    const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
-    clip = (slot / per_clip) * 8 + xcd;
-    sub = slot % per_clip;
-  } else {
-    clip = blockIdx.x / per_clip;
-    sub = blockIdx.x % per_clip;
-  }
+  block_to_clip(n_clips, bins * n_yt, clip, sub);
   const int b = sub / n_yt, yt = sub % n_yt;
   const int y0 = yt * tile_rows, y1 = (y0 + tile_rows < H) ? y0 + tile_rows : H;
   const int tile_elems = (y1 - y0) * W;
@@ -577,12 +535,7 @@ __global__ __launch_bounds__(VB_THREADS) void voxel_bin_packed_kernel(const uint
     }
   }
   __syncthreads();
-  if ((W & 3) == 0) {
-    for (int i = threadIdx.x; i < tile_elems / 4; i += VB_THREADS)
-      reinterpret_cast<float4 *>(dst)[i] = reinterpret_cast<const float4 *>(tile)[i];
-  } else {
-    for (int i = threadIdx.x; i < tile_elems; i += VB_THREADS) dst[i] = tile[i];
-  }
+  flush_tile(tile, tile_elems, W, dst);
 }
 
 // algo 1: two global float atomics per event into a pre-zeroed grid
@@ -630,6 +583,33 @@ __global__ __launch_bounds__(256) void sorted_check_kernel(const double *events,
 
 }  // namespace
 
+// ---- host side of the LDS-binned forms -----------------------------------------------------------------------------------------------
+// rows of a y-tile: as many as `budget` bytes of LDS hold (big tiles halve the slab re-reads; measured best), balanced over the tiles
+static int balanced_tile_rows(int H, int W, size_t cell, size_t budget) {
+  const int max_rows = (int)(budget / ((size_t)W * cell));
+  const int rows = max_rows < 1 ? 1 : (max_rows > H ? H : max_rows);
+  const int n_yt = (H + rows - 1) / rows;
+  return (H + n_yt - 1) / n_yt;
+}
+
+// dynamic LDS above 48 KiB has to be reserved per kernel
+static int reserve_lds(const void *kern, size_t smem, const char *who) {
+  if (smem <= 48 * 1024) return EVP_OK;
+  hipError_t e = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
+  EVP_CHECK_ARG(e == hipSuccess, EVP_ELAUNCH, "%s: cannot reserve %zu B of LDS: %s", who, smem, hipGetErrorString(e));
+  return EVP_OK;
+}
+
+// launch(mode) once, or, in the verified mode 2, twice: the fast pass, then the repair pass (mode 3) for the clips it flagged
+template <typename F>
+static int launch_passes(int mode, const char *what, F launch) {
+  for (int pass = 0; pass < (mode == 2 ? 2 : 1); ++pass) {
+    launch(pass ? 3 : mode);
+    EVP_CHECK_LAUNCH(what);
+  }
+  return EVP_OK;
+}
+
 static int g_voxel_dbg = 0;
 extern "C" int evp_voxel_set_debug(int v) { const int old = g_voxel_dbg; g_voxel_dbg = v; return old; }
 
@@ -655,13 +635,8 @@ extern "C" int evp_voxel_scatter_scaled_f32(const double *events, const int64_t 
   EVP_CHECK_ARG(workspace, EVP_EINVAL, "evp_voxel_scatter_f32: workspace required for the LDS-binned algorithms");
   EVP_CHECK_ARG(algo != 2 || (n_events_total > 0 && (int64_t)H * W <= (1 << 24)), EVP_ESHAPE,
                 "evp_voxel_scatter_f32: algo 2 needs n_events_total and H*W <= 2^24");
-  if (tile_rows <= 0) {
-    // f32 cells: <= 100 KiB of LDS (big tiles halve the slab re-reads; measured best); f64 cells: <= 150 KiB, three y-tiles at 224 x 224
-    const int max_rows = (int)(((f64_cells ? 150 : 100) * 1024) / ((size_t)W * cell));
-    tile_rows = max_rows < 1 ? 1 : (max_rows > H ? H : max_rows);
-    const int nyt = (H + tile_rows - 1) / tile_rows;
-    tile_rows = (H + nyt - 1) / nyt;  // balance the tiles
-  }
+  // f32 cells: <= 100 KiB of LDS; f64 cells: <= 150 KiB, three y-tiles at 224 x 224
+  if (tile_rows <= 0) tile_rows = balanced_tile_rows(H, W, cell, (f64_cells ? 150 : 100) * 1024);
   EVP_CHECK_ARG((size_t)tile_rows * W * cell <= 160 * 1024, EVP_ESHAPE, "evp_voxel_scatter_f32: tile of %d rows x %d exceeds LDS", tile_rows, W);
   const int n_yt = (H + tile_rows - 1) / tile_rows;
   const size_t smem = (size_t)tile_rows * W * (algo == 2 ? sizeof(float) : cell);
@@ -678,10 +653,7 @@ extern "C" int evp_voxel_scatter_scaled_f32(const double *events, const int64_t 
     hipLaunchKernelGGL(voxel_pack_kernel, dim3(64, n_clips), dim3(256), 0, s, events, clip_offsets, bins, H, W, is_txyp, scale_x,
                        scale_y, keys, vl, vr);
     EVP_CHECK_LAUNCH("evp_voxel_scatter_f32(pack)");
-    if (smem > 48 * 1024) {
-      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(voxel_bin_packed_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-      EVP_CHECK_ARG(e == hipSuccess, EVP_ELAUNCH, "evp_voxel_scatter_f32: cannot reserve %zu B of LDS: %s", smem, hipGetErrorString(e));
-    }
+    if (const int rc = reserve_lds(reinterpret_cast<const void *>(voxel_bin_packed_kernel), smem, "evp_voxel_scatter_f32")) return rc;
     hipLaunchKernelGGL(voxel_bin_packed_kernel, dim3(n_clips * bins * n_yt), dim3(VB_THREADS), smem, s, keys, vl, vr, clip_offsets, workspace,
                        n_clips, bins, H, W, assume_sorted, tile_rows, n_yt, out);
     EVP_CHECK_LAUNCH("evp_voxel_scatter_f32(bin packed)");
@@ -692,18 +664,12 @@ extern "C" int evp_voxel_scatter_scaled_f32(const double *events, const int64_t 
   if (g_voxel_dbg)
     kern = f64_cells ? (is_txyp ? voxel_bin_kernel<true, double, true> : voxel_bin_kernel<false, double, true>)
                      : (is_txyp ? voxel_bin_kernel<true, float, true> : voxel_bin_kernel<false, float, true>);
-  if (smem > 48 * 1024) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-    EVP_CHECK_ARG(e == hipSuccess, EVP_ELAUNCH, "evp_voxel_scatter_f32: cannot reserve %zu B of LDS: %s", smem, hipGetErrorString(e));
-  }
+  if (const int rc = reserve_lds(reinterpret_cast<const void *>(kern), smem, "evp_voxel_scatter_f32")) return rc;
   const int n_blocks = n_clips * (bins > 1 ? bins - 1 : 1) * n_yt;  // plane 0 and plane bins-1 share a workgroup
-  for (int pass = 0; pass < (assume_sorted == 2 ? 2 : 1); ++pass) {
-    const int mode = pass ? 3 : assume_sorted;      // verified mode: fast pass, then the repair pass for flagged clips
+  return launch_passes(assume_sorted, "evp_voxel_scatter_f32(bin)", [&](int mode) {
     hipLaunchKernelGGL(kern, dim3(n_blocks), dim3(VB_THREADS), smem, s, events, clip_offsets, workspace, n_clips, bins, H, W, mode, tile_rows,
                        n_yt, scale_x, scale_y, out, flags, g_voxel_dbg);
-    EVP_CHECK_LAUNCH("evp_voxel_scatter_f32(bin)");
-  }
-  return EVP_OK;
+  });
 }
 
 extern "C" int evp_voxel_scatter_f32(const double *events, const int64_t *clip_offsets, int n_clips, int64_t n_events_total, int bins,
@@ -739,10 +705,8 @@ extern "C" int evp_voxel_scatter_fused_algo_f32(const double *events, const int6
   const size_t bm_bytes = (size_t)bm_words * 4;
   EVP_CHECK_ARG(bm_bytes <= 48 * 1024, EVP_ESHAPE, "evp_voxel_scatter_fused_f32: windows of at most %d rows (got %lld)", 48 * 1024 * 8, (long long)max_window);
   // f32 cells: <= 100 KiB of tile (as K1); f64 cells: whatever the bitmap leaves of the 160 KiB -- three y-tiles at 224 x 224 and 180 x 240
-  const int max_rows = f64_cells ? (int)((160 * 1024 - bm_bytes) / ((size_t)W * cell)) : (int)((100 * 1024) / ((size_t)W * cell));
-  int tile_rows = max_rows < 1 ? 1 : (max_rows > H ? H : max_rows);
+  const int tile_rows = balanced_tile_rows(H, W, cell, f64_cells ? 160 * 1024 - bm_bytes : 100 * 1024);
   const int n_yt = (H + tile_rows - 1) / tile_rows;
-  tile_rows = (H + n_yt - 1) / n_yt;
   const size_t smem = (size_t)tile_rows * W * cell + bm_bytes;
   EVP_CHECK_ARG(smem <= 160 * 1024, EVP_ESHAPE, "evp_voxel_scatter_fused_f32: tile of %d rows x %d + bitmap exceeds LDS", tile_rows, W);
   int64_t *cuts = workspace;
@@ -752,18 +716,13 @@ extern "C" int evp_voxel_scatter_fused_algo_f32(const double *events, const int6
                      cuts, flags, info);
   EVP_CHECK_LAUNCH("evp_voxel_scatter_fused_f32(cuts)");
   auto kern = f64_cells ? voxel_bin_fused_kernel<double> : voxel_bin_fused_kernel<float>;
-  if (smem > 48 * 1024) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-    EVP_CHECK_ARG(e == hipSuccess, EVP_ELAUNCH, "evp_voxel_scatter_fused_f32: cannot reserve %zu B of LDS: %s", smem, hipGetErrorString(e));
-  }
+  if (const int rc = reserve_lds(reinterpret_cast<const void *>(kern), smem, "evp_voxel_scatter_fused_f32")) return rc;
   const int n_blocks = n_clips * (bins > 1 ? bins - 1 : 1) * n_yt;
-  for (int pass = 0; pass < 2; ++pass) {
+  return launch_passes(2, "evp_voxel_scatter_fused_f32(bin)", [&](int mode) {
     hipLaunchKernelGGL(kern, dim3(n_blocks), dim3(VB_THREADS), smem, s, events, win_begin, win_end, erase_idx, erase_offsets, added_rows,
-                       add_offsets, cuts, info, n_clips, bins, H, W, pass ? 3 : 2, tile_rows, n_yt, bm_words, scale_x, scale_y, out, flags, view_params,
+                       add_offsets, cuts, info, n_clips, bins, H, W, mode, tile_rows, n_yt, bm_words, scale_x, scale_y, out, flags, view_params,
                        view_h, view_w, negate_on_time_flip);
-    EVP_CHECK_LAUNCH("evp_voxel_scatter_fused_f32(bin)");
-  }
-  return EVP_OK;
+  });
 }
 
 extern "C" int evp_voxel_scatter_fused_f32(const double *events, const int64_t *win_begin, const int64_t *win_end, int n_clips,
