@@ -88,6 +88,8 @@ SIGNATURES = {
     "evp_adamw_multi": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _f, _f, _f, _f, _i, _f, _vp, _vp],
     "evp_grad_norm_multi": [_vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp],
     "evp_grad_clip_multi": [_vp, _vp, _vp, _vp, _i, _i, _vp, _d, _vp, _vp, _vp],
+    "evp_grad_guard_multi": [_vp, _vp, _vp, _vp, _i, _i, _vp, _d, _d, _d, _vp, _vp, _vp, _vp],
+    "evp_adamw_guarded_multi": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _f, _f, _f, _f, _i, _f, _vp, _vp, _vp],
     "evp_batchnorm_fwd": [_vp, _i, _i64, _i, _vp, _vp, _f, _f, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "evp_batchnorm_bwd": [_vp, _vp, _vp, _i, _i64, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp],
     "evp_batchnorm_nblk": [_i64],

@@ -8,7 +8,10 @@ executor runs a few eager steps (allocator and autograd warm-up, on the capture 
              place) while the next chunk computes -> [AdamW]
 
 (`clip_grad`: evp_grad_clip_multi sits in front of AdamW inside the same graph -- the norm and the coefficient never leave
-the device; with N ranks the global norm needs every buffer reduced, so the update is one launch after the last all-reduce.)
+the device; with N ranks the global norm needs every buffer reduced, so the update is one launch after the last all-reduce.
+`skip_nonfinite`: evp_grad_guard_multi takes that place and the update behind it is left out, on the device, when a gradient holds an
+Inf or NaN -- with N ranks the guard judges the all-reduced gradients, so one rank's NaN reaches every rank through the SUM and all
+ranks skip together.)
 
 and from then on a step is: copy the batch into the static input buffers, draw the mask noise into its static buffer,
 stage the optimizer's per-step scalars (lr, bias corrections) into the pinned table the graph's own H2D node re-reads,
@@ -125,7 +128,8 @@ class _GraphSeq:
 
 class GraphedStep:
     def __init__(self, model, optimizer, forward, static_inputs, noise_shape=None, generator=None, reducer=None,
-                 use_graph=True, warmup=2, wgrad_chunks=4, step_prepare=None, host_generator=None, backward_cut=None, clip_grad=None):
+                 use_graph=True, warmup=2, wgrad_chunks=4, step_prepare=None, host_generator=None, backward_cut=None, clip_grad=None,
+                 skip_nonfinite=False):
         """forward(model, *static_inputs, noise) -> tuple whose first item is the loss. `static_inputs`: device tensors
         with the batch's shapes (overwritten by `step(...)` when new data is passed). `noise_shape`: (B, L) of the
         masking noise, or None when the model draws none (density masking, contrastive stage).
@@ -134,9 +138,14 @@ class GraphedStep:
         hook before anything is launched and copied to the static device buffer; False = the captured graph cannot serve
         this step, which then runs eagerly with the same noise.
         `clip_grad`: torch.nn.utils.clip_grad_norm_(parameters, clip_grad) in front of every update (reference utils/misc.py:289-290),
-        on the device (FusedAdamW.max_grad_norm); `grad_norm` then holds {pre-clip norm, coefficient} of the last step."""
+        on the device (FusedAdamW.max_grad_norm); `grad_norm` then holds {pre-clip norm, coefficient} of the last step.
+        `skip_nonfinite`: an update whose gradients hold an Inf or NaN is left out (reference utils/misc.py:290, GradScaler.step), on
+        the device (FusedAdamW.skip_nonfinite); `guard_state` then holds {skipped this step, skipped so far, applied so far}."""
         self.model, self.opt, self.forward, self.reducer = model, optimizer, forward, reducer
         self.clip_grad = None if clip_grad is None else float(clip_grad)
+        self.skip_nonfinite = bool(skip_nonfinite)
+        if self.skip_nonfinite and not hasattr(optimizer, "skip_nonfinite"):
+            raise ValueError("GraphedStep(skip_nonfinite=True) needs a FusedAdamW (the verdict is reached on the device, inside the optimizer's launch)")
         if self.clip_grad is not None and not hasattr(optimizer, "max_grad_norm"):
             raise ValueError("GraphedStep(clip_grad=...) needs a FusedAdamW (the clip runs on the device, inside the optimizer's launch)")
         # data-parallel form only: cut the backward at the encoder / decoder boundary (two graphs, the decoder's gradients all-reduced
@@ -228,16 +237,23 @@ class GraphedStep:
 
     @contextlib.contextmanager
     def _clipping(self):
-        """The optimizer clips to this executor's clip_grad while one of its own updates is launched or captured (the optimizer is
-        the caller's: outside the executor it keeps whatever max_grad_norm it had)."""
-        if self.clip_grad is None:
+        """The optimizer clips to this executor's clip_grad, and guards with its skip_nonfinite, while one of its own updates is
+        prepared (refresh), launched or captured (the optimizer is the caller's: outside the executor it keeps whatever max_grad_norm
+        and skip_nonfinite it had)."""
+        if self.clip_grad is None and not self.skip_nonfinite:
             yield
             return
-        saved, self.opt.max_grad_norm = self.opt.max_grad_norm, self.clip_grad
+        saved = (self.opt.max_grad_norm, getattr(self.opt, "skip_nonfinite", False))
+        if self.clip_grad is not None:
+            self.opt.max_grad_norm = self.clip_grad
+        if self.skip_nonfinite:
+            self.opt.skip_nonfinite = True
         try:
             yield
         finally:
-            self.opt.max_grad_norm = saved
+            self.opt.max_grad_norm = saved[0]
+            if self.skip_nonfinite:
+                self.opt.skip_nonfinite = saved[1]
 
     def _opt_step(self):
         with self._clipping():
@@ -249,12 +265,22 @@ class GraphedStep:
         of the MEAN gradient, the same on every rank). Read it before the next step, like `loss`."""
         return self.opt.last_grad_norm if self.clip_grad is not None else None
 
+    @property
+    def guard_state(self):
+        """Static device int64 tensor {skipped this step, steps skipped so far, steps applied so far, reserved} (skip_nonfinite set;
+        the same on every rank). Read it before the next step, like `loss`."""
+        return self.opt.guard_state if self.skip_nonfinite else None
+
     # ------------------------------------------------------------------------------------------------ capture
     def _snapshot(self):
         """Everything the warm-up steps of _capture() would otherwise leave changed: weights, module buffers (BatchNorm
         statistics, MoCo queue and pointer), optimizer moments + step counter, and the mask-noise generator."""
         params = [p for p in self.model.parameters()]
-        snap = dict(params=[p.detach().clone() for p in params],
+        guarded = self.skip_nonfinite or getattr(self.opt, "_guard_live", False)
+        if guarded:
+            self.opt.skipped_steps()         # one read-back: a live guard also brings opt._step to the applied count
+        snap = dict(guarded=guarded, skipped=getattr(self.opt, "skipped_seen", 0),
+                    params=[p.detach().clone() for p in params],
                     buffers=[(b, b.detach().clone()) for b in self.model.buffers()],
                     step=self.opt._step, gen=self.gen.get_state(), host_gen=self.host_gen.get_state(), moments={})
         for p in params:
@@ -280,6 +306,9 @@ class GraphedStep:
                     st["exp_avg"].zero_()
                     st["exp_avg_sq"].zero_()
         self.opt._step = snap["step"]
+        if snap["guarded"]:                  # the guard's counters: the warm-up steps were applied (or skipped) for real
+            self.opt.skipped_seen = snap["skipped"]
+            self.opt._set_guard(snap["step"], snap["skipped"])
         self.gen.set_state(snap["gen"])
         self.host_gen.set_state(snap["host_gen"])
         ops.refresh_lp_shadows(self.model.parameters())
@@ -331,9 +360,9 @@ class GraphedStep:
                         out = self.forward(self.model, *self.inputs, self.noise)     # (a splitting gather ends / begins graphs in here)
                         out[0].backward()
                         if not self.multi:
-                            self.opt.refresh(scalars=False)
                             with self._clipping():
-                                self.opt.launch()        # (clip_grad: evp_grad_clip_multi, then AdamW)
+                                self.opt.refresh(scalars=False)
+                                self.opt.launch()        # (clip_grad: evp_grad_clip_multi, then AdamW; skip_nonfinite: the guarded pair)
                         self.loss = out[0].detach()
                         del out
                         seq.end()
@@ -370,13 +399,13 @@ class GraphedStep:
                 # AdamW in parts, each launched as soon as its gradient buffer is reduced (the graph then only holds the
                 # H2D copies of the per-step scalar tables); one launch after the last all-reduce otherwise
                 # (clip_grad: the global norm needs EVERY buffer reduced before any update -- one launch, the clip in front of it)
-                self.parts = self.plan.streams is not None and self.clip_grad is None
+                # (skip_nonfinite likewise: the verdict needs every buffer reduced)
+                self.parts = self.plan.streams is not None and self.clip_grad is None and not self.skip_nonfinite
                 g2 = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(g2, stream=side, capture_error_mode="thread_local"):
+                with torch.cuda.graph(g2, stream=side, capture_error_mode="thread_local"), self._clipping():
                     self.opt.refresh()
                     if not self.parts:
-                        with self._clipping():
-                            self.opt.launch()
+                        self.opt.launch()
                 if self.parts:
                     with torch.cuda.stream(side):
                         self.plan.attach_optimizer(self.opt, [p for p in self.model.parameters() if p.requires_grad])
@@ -387,7 +416,8 @@ class GraphedStep:
                              "%d weight-gradient chunks on two streams, each all-reduced (RCCL) while the next "
                              "computes, AdamW per reduced buffer" % self.wgrad_chunks) if self.parts else \
                             ("hip-graph (fwd+bwd) + %d weight-gradient chunks overlapped with RCCL all-reduce + hip-graph (%sAdamW)"
-                             % (self.wgrad_chunks, "clip to the norm of the mean gradient + " if self.clip_grad is not None else ""))
+                             % (self.wgrad_chunks, ("skip on non-finite gradients + " if self.skip_nonfinite else "") +
+                                ("clip to the norm of the mean gradient + " if self.clip_grad is not None else "")))
                 if fc is not None and (fc.post or fc.pre or len(seq.graphs) > 1):
                     self.note += " [forward collectives outside the graphs: %d splitting key all-gather(s), %d overlapped with the backward, " \
                                  "%d buffer broadcast(s)]" % (len(seq.graphs) - 1, len(fc.post), len(fc.pre))

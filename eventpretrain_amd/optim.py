@@ -9,6 +9,13 @@ every step. Gradient pointers are re-read every step (autograd may hand out new 
 `max_grad_norm` (None = off) clips on the device (torch.nn.utils.clip_grad_norm_, reference utils/misc.py:289-290):
 `launch()` then issues evp_grad_clip_multi in front of evp_adamw_multi, which leaves {pre-clip norm, coefficient} in
 `last_grad_norm` and the coefficient folded into the device-resident gradient scale of that one step.
+
+`skip_nonfinite` (False = off) leaves the update out when any gradient holds an Inf or NaN, as the reference's GradScaler.step
+does (utils/misc.py:290): `launch()` then issues evp_grad_guard_multi (the clip's single pass, which also tests every element)
+and evp_adamw_guarded_multi. A skipped step leaves parameters, moments, shadows and Adam's step count untouched. The count of
+APPLIED steps therefore lives on the device (`guard_state`), where the bias corrections are computed from it; `self._step`
+counts launches while the guard is on and is brought back to the applied count whenever the host reads the guard
+(state_dict(), switching the guard off).
 """
 import math
 
@@ -22,7 +29,8 @@ CHUNK = 16384
 
 
 class FusedAdamW(torch.optim.Optimizer):
-    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, grad_scale=1.0, max_grad_norm=None):
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, grad_scale=1.0, max_grad_norm=None,
+                 skip_nonfinite=False):
         defaults = dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay)
         super().__init__(params, defaults)
         b = {tuple(g["betas"]) for g in self.param_groups}
@@ -31,9 +39,13 @@ class FusedAdamW(torch.optim.Optimizer):
             raise ValueError("FusedAdamW needs one (betas, eps) for all groups")
         self.grad_scale = float(grad_scale)
         self.max_grad_norm = max_grad_norm       # an attribute, not a param_group entry: the checkpoint layout stays AdamW's
+        self.skip_nonfinite = bool(skip_nonfinite)   # likewise an attribute: a property of the run, not of the checkpoint
         self._step = 0
         self._tabs = None
         self._sig = None
+        self._guard = None           # device int64 [4] {skipped this step, skipped total, applied steps, reserved}: made once, kept
+        self._guard_live = False     # the device's applied count is the truth (guarded launches since it was seeded from _step)
+        self.skipped_seen = 0        # guard[1] as of the host's last read (skipped_steps())
 
     # ------------------------------------------------------------------------------------------------ tables
     def _active(self):
@@ -88,7 +100,49 @@ class FusedAdamW(torch.optim.Optimizer):
         for k in ("grads", "lp", "wd", "lr", "hyper"):       # numpy views of the pinned tables: cheap element writes
             T["n_" + k] = T["h_" + k].numpy()
         T["group_of"] = np.array([gi for gi, _ in act], dtype=np.int64)
+        if self._guard is None or self._guard.device != dev:
+            self._guard, self._guard_live = torch.zeros(4, dtype=torch.int64, device=dev), False
         return T
+
+    # ------------------------------------------------------------------------------------------------ guard
+    def _set_guard(self, applied, skipped):
+        """In place (a captured graph keeps writing this tensor): {0, skipped, applied, 0}."""
+        if self._guard is not None:
+            self._guard.copy_(torch.tensor([0, int(skipped), int(applied), 0], dtype=torch.int64))
+
+    def _read_guard(self):
+        """One read-back of the guard; while it is live the host's step count follows the device's applied count."""
+        g = self._guard.tolist()
+        self.skipped_seen = int(g[1])
+        if self._guard_live:
+            self._step = int(g[2])
+        return g
+
+    def _guard_handover(self):
+        """Host side of switching the guard on or off between two launches: on, the device's applied count is seeded from
+        `_step`; off, `_step` takes the applied count back (one read-back). Neither can happen inside a graph capture."""
+        if self.skip_nonfinite == self._guard_live or self._guard is None:
+            return
+        if torch.cuda.is_current_stream_capturing():
+            raise _lib.EvpError("FusedAdamW: skip_nonfinite was switched while a graph is being captured; run one eager step first")
+        if self.skip_nonfinite:
+            self._set_guard(self._step, self.skipped_seen)
+            self._guard_live = True
+        else:
+            self._read_guard()
+            self._guard_live = False
+
+    @property
+    def guard_state(self):
+        """Static device int64 [4] {skipped this step, steps skipped so far, steps applied so far, reserved} written by every
+        launch() with `skip_nonfinite` on (a captured graph keeps writing this same tensor); None before the first refresh()."""
+        return self._guard
+
+    def skipped_steps(self):
+        """Steps skipped so far (one read-back)."""
+        if self._guard is None:
+            return 0
+        return int(self._read_guard()[1])
 
     def refresh(self, advance=True, scalars=True):
         """Host side of a step: (re)build tables if the set of parameters with gradients changed, bump the step
@@ -106,6 +160,8 @@ class FusedAdamW(torch.optim.Optimizer):
             self._tabs, self._sig = self._build(act), sig
         T = self._tabs
         self._act = act
+        if advance:                     # (grad_norm() only reads the gradients: it leaves the guard to whoever launches updates)
+            self._guard_handover()
         ng, nl = T["n_grads"], T["n_lp"]
         for i, (gi, p) in enumerate(act):
             g = p.grad
@@ -145,7 +201,10 @@ class FusedAdamW(torch.optim.Optimizer):
     def state_dict(self):
         """torch.optim.AdamW layout (step / exp_avg / exp_avg_sq per parameter), so checkpoints interchange with the
         reference's optimizer (utils/misc.py:353-359). The kernel keeps ONE step counter; it is written into every
-        parameter's `step` entry here."""
+        parameter's `step` entry here -- with the guard on, the count of APPLIED steps (one read-back), so that a resumed run
+        continues Adam's bias corrections where the reference's would."""
+        if self._guard_live:
+            self._read_guard()
         for st in self.state.values():
             if "exp_avg" in st:
                 st["step"] = torch.tensor(float(self._step))
@@ -160,6 +219,7 @@ class FusedAdamW(torch.optim.Optimizer):
                 if k in st and (st[k].dtype != torch.float32 or not st[k].is_contiguous()):
                     st[k] = st[k].float().contiguous()
         self._tabs, self._sig = None, None       # the moments are new tensors: rebuild the pointer tables
+        self._guard_live = False                 # the applied count is seeded from the loaded step at the next refresh()
 
     @torch.no_grad()
     def reset_state(self):
@@ -169,18 +229,35 @@ class FusedAdamW(torch.optim.Optimizer):
                 st["exp_avg"].zero_()
                 st["exp_avg_sq"].zero_()
         self._step = 0
+        self.skipped_seen = 0
+        if self._guard is not None:
+            self._guard.zero_()
 
     @property
     def last_grad_norm(self):
         """Static device tensor {pre-clip norm of the applied gradient, clip coefficient} written by the last launch() with
-        `max_grad_norm` set (a captured graph keeps writing this same tensor); None before the first refresh()."""
+        `max_grad_norm` or `skip_nonfinite` set (a captured graph keeps writing this same tensor; a skipped step leaves {NaN, 0},
+        an unclipped guarded one {norm, 1}); None before the first refresh()."""
         return None if self._tabs is None else self._tabs["clip_out"]
 
     def launch(self):
         """Device side of a step (graph-capturable): one evp_adamw_multi over all chunks; with `max_grad_norm` set,
-        evp_grad_clip_multi in front of it scales this step's device-resident gradient scale by the clip coefficient."""
+        evp_grad_clip_multi in front of it scales this step's device-resident gradient scale by the clip coefficient; with
+        `skip_nonfinite`, evp_grad_guard_multi (verdict, applied-step count and bias corrections, clip) and the guarded update."""
         T = self._tabs
         b1, b2 = self.param_groups[0]["betas"]
+        if self.skip_nonfinite:
+            if not self._guard_live:
+                raise _lib.EvpError("FusedAdamW.launch: skip_nonfinite was switched on after the last refresh()")
+            call("evp_grad_guard_multi", T["grads"].data_ptr(), T["numel"].data_ptr(), T["chunk_t"].data_ptr(),
+                 T["chunk_o"].data_ptr(), T["n_chunks"], CHUNK, T["norm_ws"].data_ptr(),
+                 0.0 if self.max_grad_norm is None else float(self.max_grad_norm), float(b1), float(b2), T["hyper"].data_ptr(),
+                 T["clip_out"].data_ptr(), self._guard.data_ptr(), stream_ptr())
+            call("evp_adamw_guarded_multi", T["params"].data_ptr(), T["grads"].data_ptr(), T["m"].data_ptr(), T["v"].data_ptr(),
+                 T["lp"].data_ptr(), T["numel"].data_ptr(), T["wd"].data_ptr(), T["lr"].data_ptr(), T["chunk_t"].data_ptr(),
+                 T["chunk_o"].data_ptr(), T["n_chunks"], CHUNK, 1.0, float(b1), float(b2), float(self.param_groups[0]["eps"]),
+                 max(self._step, 1), self.grad_scale, T["hyper"].data_ptr(), self._guard.data_ptr(), stream_ptr())
+            return
         if self.max_grad_norm is not None:
             call("evp_grad_clip_multi", T["grads"].data_ptr(), T["numel"].data_ptr(), T["chunk_t"].data_ptr(),
                  T["chunk_o"].data_ptr(), T["n_chunks"], CHUNK, T["norm_ws"].data_ptr(), float(self.max_grad_norm),
@@ -219,6 +296,9 @@ class FusedAdamW(torch.optim.Optimizer):
         if self.max_grad_norm is not None:
             raise _lib.EvpError("launch_part: max_grad_norm is set -- the global norm needs every gradient buffer reduced before "
                                 "any update; use launch()")
+        if self.skip_nonfinite:
+            raise _lib.EvpError("launch_part: skip_nonfinite is set -- the verdict needs every gradient buffer reduced before any "
+                                "update; use launch()")
         part = self._parts[i]
         if part is None:
             return

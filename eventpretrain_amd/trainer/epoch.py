@@ -88,7 +88,7 @@ class DeferredLosses:
 def auto_executor(args, model, optimizer, loss_name, build, extra=()):
     """The step executor an epoch loop builds by itself on its first batch and keeps on the model, in `model._evp_auto_executor`
     as (key, executor): `build()` makes it, once per (optimizer, loss name, compute dtype, *extra) -- `extra` is what else is
-    captured with the step (fine-tuning: clip_grad); a change of any of these builds anew. The batch shape is not in the key:
+    captured with the step (fine-tuning: clip_grad; skip_nonfinite when on); a change of any of these builds anew. The batch shape is not in the key:
     an executor captured at another shape is handed back and the loop steps it eagerly (eager_step_with). None where a captured
     step cannot stand in for the eager loop: `args.graph_step = False` (the opt-out), gradient accumulation, backward off, a
     device that is not CUDA, an optimizer that is not FusedAdamW, a forward replaced on the instance."""
@@ -127,7 +127,31 @@ def run_epoch(args, model, data_loader, optimizer, epoch, loss_scaler, log_write
     meter_divided   the fine-tuning order (reference ft_cls_trainer.py:66-77): the loss is divided inside `if args.backward` and the
                     meter gets it afterwards; pre-training (False) meters first and divides whether or not backward is on.
     vis_hook        called per step under test_experiment and visualize, and on the last batch when the epoch is a vis_train_freq'th
-                    (`vis_last_batch`: the joint epoch has only ever drawn per step)."""
+                    (`vis_last_batch`: the joint epoch has only ever drawn per step).
+    `args.skip_nonfinite` (default False; FusedAdamW only): an optimizer step whose gradients hold an Inf or NaN is left out, on the
+    device, as the reference's GradScaler.step does (utils/misc.py:290). The returned dict then gains `skipped_steps`, this epoch's
+    count (one read-back, at the end). The metered loss of such a batch stays what it is: the guard protects the weights, not the log."""
+    skip = bool(getattr(args, "skip_nonfinite", False))
+    if not skip:
+        return _run_epoch(args, model, data_loader, optimizer, epoch, loss_scaler, log_writer, loss_names, eager_step, build_executor,
+                          step_executor, clip_grad, meter_divided, vis_hook, vis_last_batch)
+    if not hasattr(optimizer, "skip_nonfinite"):
+        raise ValueError("args.skip_nonfinite needs a FusedAdamW (the verdict is reached on the device, inside the optimizer's launch)")
+    if step_executor is not None and not getattr(step_executor, "skip_nonfinite", False):
+        raise ValueError("args.skip_nonfinite is set but the given step_executor was built without skip_nonfinite=True")
+    before = optimizer.skipped_seen          # the host's last reading: the end of the epoch before, or 0
+    saved, optimizer.skip_nonfinite = optimizer.skip_nonfinite, True      # the eager steps of this epoch guard too
+    try:
+        stats = _run_epoch(args, model, data_loader, optimizer, epoch, loss_scaler, log_writer, loss_names, eager_step, build_executor,
+                           step_executor, clip_grad, meter_divided, vis_hook, vis_last_batch)
+    finally:
+        optimizer.skip_nonfinite = saved
+    stats["skipped_steps"] = optimizer.skipped_steps() - before
+    return stats
+
+
+def _run_epoch(args, model, data_loader, optimizer, epoch, loss_scaler, log_writer, loss_names, eager_step, build_executor,
+               step_executor, clip_grad, meter_divided, vis_hook, vis_last_batch):
     model.train(True)
     logger = misc.MetricLogger(delimiter="  ")
     logger.add_meter("lr", misc.SmoothedValue(window_size=1, fmt="{value:.6f}"))

@@ -31,18 +31,20 @@ def auto_ft_step_executor(args, model, optimizer, loss_scaler, batch_tensors):
     regularisers of the recipe replay correctly: the DropPath draws and the dropout keys come from torch's device generator, which
     advances under replay (ops.draw_block_drop / draw_drop_seed). `args.clip_grad` (the reference's default recipe: --clip_grad 5) is
     captured with the step: norm, coefficient and the scaled update stay on the device (evp_grad_clip_multi); a changed value
-    re-captures. Returns None where trainer.epoch.auto_executor refuses: gradient accumulation, backward off, an optimizer that is
+    re-captures. `args.skip_nonfinite` is captured likewise (evp_grad_guard_multi in that place). Returns None where trainer.epoch.auto_executor refuses: gradient accumulation, backward off, an optimizer that is
     not FusedAdamW, a CPU device, or `args.graph_step = False`."""
     x, y = batch_tensors
     clip = getattr(args, "clip_grad", None)
     clip = None if clip is None else float(clip)
+    skip = bool(getattr(args, "skip_nonfinite", False))
 
     def build():
         from ...engine import GraphedStep
         smoothing = float(getattr(args, "smoothing", 0) or 0)
         fwd = lambda m, x_, y_, noise: (ops.CrossEntropyFn.apply(m(x_)[-2], y_, smoothing),)
-        return GraphedStep(model, optimizer, fwd, [x.clone(), y.clone()], reducer=getattr(loss_scaler, "reducer", None), clip_grad=clip)
-    return auto_executor(args, model, optimizer, "loss_cls", build, extra=(clip,))
+        return GraphedStep(model, optimizer, fwd, [x.clone(), y.clone()], reducer=getattr(loss_scaler, "reducer", None), clip_grad=clip,
+                           skip_nonfinite=skip)
+    return auto_executor(args, model, optimizer, "loss_cls", build, extra=(clip, skip))
 
 
 def ft_train_one_epoch(args, model, data_loader, optimizer, epoch, loss_scaler, log_writer=None, evrepsl_model=None):

@@ -18,6 +18,7 @@ def auto_step_executor(args, model, optimizer, loss_scaler, batch_tensors, loss_
     if vis_hook is not None and args.visualize:
         return None
     x, y = batch_tensors
+    skip = bool(getattr(args, "skip_nonfinite", False))      # captured with the step (evp_grad_guard_multi in front of the update)
 
     def build():
         from ...engine import GraphedStep
@@ -34,8 +35,8 @@ def auto_step_executor(args, model, optimizer, loss_scaler, batch_tensors, loss_
         seed = int(torch.empty((), dtype=torch.int64).random_().item())      # follows torch.manual_seed like the eager draw would
         return GraphedStep(model, optimizer, fwd, [x.clone(), y.clone()], noise_shape=noise_shape,
                            generator=torch.Generator(device=x.device).manual_seed(seed), reducer=getattr(loss_scaler, "reducer", None),
-                           step_prepare=step_prepare, host_generator=torch.Generator().manual_seed(seed))
-    return auto_executor(args, model, optimizer, loss_name, build)
+                           step_prepare=step_prepare, host_generator=torch.Generator().manual_seed(seed), skip_nonfinite=skip)
+    return auto_executor(args, model, optimizer, loss_name, build, extra=(skip,))
 
 
 def _epoch(args, model, data_loader, optimizer, epoch, loss_scaler, log_writer, loss_name, forward, vis_hook, step_executor=None, auto=True):

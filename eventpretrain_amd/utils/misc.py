@@ -194,8 +194,9 @@ def get_grad_norm_(parameters, norm_type: float = 2.0, optimizer=None):
 class NativeScalerWithGradNormCount:
     """Callable with the reference's signature (utils/misc.py:274-300). The reference wraps a fp16 GradScaler; this
     path computes in bf16 / f32 with f32 accumulation, which needs no loss scaling, so the object only sequences
-    backward -> (data-parallel gradient all-reduce) -> grad norm -> optimizer step. state_dict() keeps the key layout of
-    a disabled GradScaler.
+    backward -> (data-parallel gradient all-reduce) -> grad norm -> optimizer step. What GradScaler.step() does besides scaling --
+    leaving the step out when a gradient holds an Inf or NaN (:290) -- is FusedAdamW(skip_nonfinite=True), decided on the device.
+    state_dict() keeps the key layout of a disabled GradScaler.
 
     `reducer` (a parallel.BucketedGradReducer, here or per call) takes the place of the reference's DDP wrap
     (main_pretrain.py:319): after the LAST accumulation backward of an optimizer step it SUM-all-reduces the gradients;
@@ -217,14 +218,18 @@ class NativeScalerWithGradNormCount:
         if reducer is not None:
             reducer.finish()
         from ..optim import FusedAdamW
-        if clip_grad is not None and isinstance(optimizer, FusedAdamW):
+        guarded = isinstance(optimizer, FusedAdamW) and optimizer.skip_nonfinite
+        if (clip_grad is not None or guarded) and isinstance(optimizer, FusedAdamW):
             # torch.nn.utils.clip_grad_norm_(parameters, clip_grad) (reference utils/misc.py:289-290): every gradient times
             # min(1, clip / (total_norm + 1e-6)). FusedAdamW computes the norm and the coefficient on the device
             # (evp_grad_clip_multi) and folds the coefficient into the gradient scale its kernel applies as it reads each
             # gradient: no pass over the gradients, no read-back. The returned norm is the pre-clip total norm of the
             # gradient the optimizer applies (the mean over ranks), as clip_grad_norm_ returns -- a device scalar.
+            # FusedAdamW.skip_nonfinite (the step the reference's GradScaler.step takes or leaves, utils/misc.py:290) is the same
+            # pass with or without a clip (evp_grad_guard_multi): the verdict stays on the device too, no host read here.
             saved = optimizer.max_grad_norm
-            optimizer.max_grad_norm = float(clip_grad)
+            if clip_grad is not None:
+                optimizer.max_grad_norm = float(clip_grad)
             try:
                 optimizer.step()
             finally:

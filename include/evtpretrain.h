@@ -390,6 +390,28 @@ int evp_grad_norm_multi(const float *const *grads, const int64_t *numel, const i
 int evp_grad_clip_multi(const float *const *grads, const int64_t *numel, const int32_t *chunk_tensor,
                         const int64_t *chunk_offset, int n_chunks, int chunk_elems, float *workspace, double max_norm,
                         float *hyper, float *out, void *stream);
+/* utils/misc.py:290 (`self._scaler.step(optimizer)`: GradScaler skips optimizer.step() when any gradient holds an Inf or NaN) with
+ * the norm and the clip of utils/misc.py:285-289 in the same single pass, without a host decision. In stream order: every chunk is
+ * summed as evp_grad_clip_multi sums it and every element read is tested for finiteness; a chunk with a non-finite element
+ * leaves NaN as its partial. guard is a device int64 [4] = {skipped this step, steps skipped so far, steps applied so far (Adam's
+ * t), reserved}. Some partial NaN: guard[0] = 1, guard[1] += 1, out = {NaN, 0}, hyper untouched. Otherwise guard[0] = 0,
+ * t = ++guard[2], hyper[0] = (float)(1 - beta1^t), hyper[1] = (float)sqrt(1 - beta2^t) (double arithmetic: the betas come as
+ * doubles so that these are the host's own values rounded once), and with max_norm > 0 norm, coefficient and hyper[2] exactly as
+ * evp_grad_clip_multi leaves them -- a sum that overflowed over finite elements gives norm = +Inf, coef = 0, which is what
+ * clip_grad_norm_ does and not a skip; max_norm == 0 clips nothing: out = {norm, 1}. evp_adamw_guarded_multi behind it in the same
+ * stream applies or skips the step. Two launches, no atomics, no extra memory. max_norm finite, >= 0; betas in (0, 1). */
+int evp_grad_guard_multi(const float *const *grads, const int64_t *numel, const int32_t *chunk_tensor,
+                         const int64_t *chunk_offset, int n_chunks, int chunk_elems, float *workspace, double max_norm,
+                         double beta1, double beta2, float *hyper, float *out, int64_t *guard, void *stream);
+/* utils/misc.py:290, the step GradScaler.step() takes or leaves: evp_adamw_multi with the verdict of evp_grad_guard_multi in front
+ * of `stream`. Every workgroup reads guard[0] once and returns before it touches anything when it is non-zero: parameters, both
+ * moments and the bf16 shadows of a skipped step are not written at all. Otherwise evp_adamw_multi's arithmetic (the same kernel).
+ * guard and dev_hyper must not be NULL (the bias corrections are the ones evp_grad_guard_multi wrote for the applied count). */
+int evp_adamw_guarded_multi(float *const *params, const float *const *grads, float *const *exp_avg, float *const *exp_avg_sq,
+                            uint16_t *const *lp_shadow, const int64_t *numel, const float *weight_decay, const float *lr_scale,
+                            const int32_t *chunk_tensor, const int64_t *chunk_offset, int n_chunks, int chunk_elems, float lr,
+                            float beta1, float beta2, float eps, int step, float grad_scale, const float *dev_hyper,
+                            const int64_t *guard, void *stream);
 
 /* ------------------------------------------------------------------------------------------------ K13 BatchNorm on tokens
  * mlp_head.py:13,18 applied as pr_hub_model.py:223-237 does: per-channel batch statistics over the B*L rows of
