@@ -225,7 +225,7 @@ def _tiles(shape, tile):
 def families(tensor, shape, heads=None):
     """-> (the 2-D view's shape, {family: [(row slice, column slice), ...]}) for the tensor called `tensor`."""
     fam = {}
-    if tensor in ("out", "dx"):
+    if tensor in ("out", "dx") or tensor.startswith("act:"):       # "act:...": the [M, D] tensors of tests/contrast_truth.py
         v = (math.prod(shape[:-1]), shape[-1])
         fam["tile16x64"] = _tiles(v, ACT_TILE)
     elif tensor == "attn":
