@@ -231,6 +231,29 @@ def convvit_masked(sd, x, noise, *, heads, mask_ratio, fusion=True, pre="backbon
     return l1, l2, layer_norm(fused, sd[pre + "norm_layer.weight"], sd[pre + "norm_layer.bias"], 1e-6), mask, ids_restore
 
 
+def convvit_dense(sd, x, *, heads, pre="backbone."):
+    """convvit.py:173-207 (pretrain phases): the three stages without a keep mask, every token through the ViT blocks, the last
+    of which returns its probabilities; LN of the last block's output alone."""
+    t = _patch_embed_map(sd, pre + "patch_embed1.", x, 4)
+    for i in range(_depth(sd, pre + "conv_block1.")):
+        t = conv_block(sd, f"{pre}conv_block1.{i}.", t)
+    l1 = t
+    t = _patch_embed_map(sd, pre + "patch_embed2.", t, 2)
+    for i in range(_depth(sd, pre + "conv_block2.")):
+        t = conv_block(sd, f"{pre}conv_block2.{i}.", t)
+    l2 = t
+    t = _patch_embed_map(sd, pre + "patch_embed3.", t, 2).flatten(2).transpose(1, 2)
+    t = F.linear(t, sd[pre + "patch_embed4.weight"], sd[pre + "patch_embed4.bias"]) + sd[pre + "pos_embed"]
+    n = _depth(sd, pre + "vit_block.")
+    attn = None
+    for i in range(n):
+        if i < n - 1:
+            t = vit_block(sd, f"{pre}vit_block.{i}.", t, heads)
+        else:
+            t, attn = vit_block(sd, f"{pre}vit_block.{i}.", t, heads, want_attn=True)
+    return l1, l2, layer_norm(t, sd[pre + "norm_layer.weight"], sd[pre + "norm_layer.bias"], 1e-6), attn
+
+
 def convvit_rec_step(sd, x, target, noise, cfg):
     l1, l2, lh, mask, ids_restore = convvit_masked(sd, x, noise, heads=cfg["heads"], mask_ratio=cfg["mask_ratio"])
     pred = rec_decoder(sd, lh, ids_restore, heads=cfg["dec_heads"])
@@ -425,7 +448,7 @@ def swin_masked(sd, x, noise, cfg, fusion=True, pre="backbone."):
         for s in range(len(outs) - 1):
             e, c = outs[s]
             r = res >> s
-            dense = torch.zeros(B, r * r, e.shape[-1])
+            dense = torch.zeros(B, r * r, e.shape[-1], dtype=e.dtype)
             dense[:, c[:, 0] * r + c[:, 1]] = e
             dense = dense.view(B, r, r, -1).permute(0, 3, 1, 2)
             k = r // g
@@ -605,15 +628,19 @@ def swin_con_step(sd, x, clip_emb, cfg, training=True):
 
 
 # ----------------------------------------------------------------------------- model/finetune_cls/ft_cls_hub_model.py:118-139
-def ft_cls_step(sd, x, label, cfg):
-    """Dense backbone (vit.py:132-156 / swin.py:248-290) -> mean over tokens -> Linear head -> mean cross-entropy
-    (trainer/finetune_cls/ft_cls_trainer.py:66). Returns (loss, pred, emb_h, attn)."""
+def ft_cls_step(sd, x, label, cfg, smoothing=0.0, want_taps=False):
+    """Dense backbone (vit.py:132-156 / swin.py:248-290 / convvit.py:173-207) -> mean over tokens -> Linear head -> mean cross-entropy
+    (trainer/finetune_cls/ft_cls_trainer.py:66), or label_smoothing_ce when `smoothing` > 0 (:63-64). Returns (loss, pred, emb_h, attn)
+    and, with `want_taps`, the backbone's stage taps as a fifth item (swin: [(tokens, coords)] per stage; else (emb_l1, emb_l2))."""
     if cfg["backbone"] == "swin":
-        _, emb_h, attn = swin_dense(sd, x, cfg)
+        taps, emb_h, attn = swin_dense(sd, x, cfg)
+    elif cfg["backbone"] == "convvit":
+        *taps, emb_h, attn = convvit_dense(sd, x, heads=cfg["heads"])
     else:
-        _, _, emb_h, attn = vit_dense(sd, x, patch=cfg["patch"], heads=cfg["heads"])
+        *taps, emb_h, attn = vit_dense(sd, x, patch=cfg["patch"], heads=cfg["heads"])
     pred = F.linear(emb_h.mean(dim=1), sd["classify_head.weight"], sd["classify_head.bias"])
-    return F.cross_entropy(pred, label), pred, emb_h, attn
+    loss = label_smoothing_ce(pred, label, smoothing) if smoothing else F.cross_entropy(pred, label)
+    return (loss, pred, emb_h, attn, taps) if want_taps else (loss, pred, emb_h, attn)
 
 
 def label_smoothing_ce(pred, label, smoothing):

@@ -20,6 +20,7 @@ Gates, all measured against the yardstick, FACTOR being the only constant:
   3. scale         |<got, T> / <T, T> - 1| <= FACTOR * e_ref. Rounding noise is near zero-mean; a missing 1 / keep_prob, 1 / R or
      d_h^-0.5 is not.
 The yardstick is computed here at run time (milliseconds at these shapes), never from the code under test."""
+import collections.abc
 import contextlib
 import functools
 import math
@@ -273,11 +274,21 @@ def compare(tensor, got, T, Y, heads=None, factor=FACTOR, blocks=True):
     return rows, fails
 
 
+def heads_for(heads, tensor):
+    """`heads` as compare_all takes it -- one number, a mapping or a callable from tensor name to head count -- for one tensor."""
+    if callable(heads):
+        return heads(tensor)
+    if isinstance(heads, collections.abc.Mapping):
+        return heads.get(tensor)
+    return heads
+
+
 def compare_all(got, ref, heads=None, factors=None, blocks=True):
-    """Every tensor of `got` against the reference. -> (failures, (worst ratio, "tensor/gate"), table as text)."""
+    """Every tensor of `got` against the reference. `heads`: one head count for all tensors, or a mapping / callable from tensor name
+    to head count (tests/backbone_truth.py: the Swin stages differ). -> (failures, (worst ratio, "tensor/gate"), table as text)."""
     fails, worst, lines = [], (0.0, ""), []
     for t, g in got.items():
-        rows, f = compare(t, g, ref.T[t], ref.Y[t], heads=heads, factor=(factors or {}).get(t, FACTOR), blocks=blocks)
+        rows, f = compare(t, g, ref.T[t], ref.Y[t], heads=heads_for(heads, t), factor=(factors or {}).get(t, FACTOR), blocks=blocks)
         fails += f
         for gate, val, bound, ratio in rows:
             worst = max(worst, (ratio, f"{t}/{gate}"))

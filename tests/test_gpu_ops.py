@@ -14,7 +14,7 @@ def _g(seed):
     return torch.Generator().manual_seed(seed)
 
 
-@pytest.mark.parametrize("D", [192, 512, 768, 4096, 128])
+@pytest.mark.parametrize("D", [192, 512, 768, 4096, 128, 32, 64, 96, 384, 1536])
 def test_layernorm_fwd_bwd(D):
     from eventpretrain_amd import ops
     g = _g(D)

@@ -36,7 +36,7 @@ def _ref_window_attention(qkv, table, rel, nG, heads):
 
 
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
-@pytest.mark.parametrize("Bg,nG,N,H", [(6, 3, 49, 3), (2, 1, 96, 12), (4, 2, 24, 24), (3, 3, 1, 6), (2, 1, 128, 3)])
+@pytest.mark.parametrize("Bg,nG,N,H", [(6, 3, 49, 3), (2, 1, 96, 12), (4, 2, 24, 24), (3, 3, 1, 6), (2, 1, 128, 3), (4, 2, 49, 1), (4, 2, 96, 2)])
 def test_window_attention_fwd_bwd(dtype, Bg, nG, N, H):
     from eventpretrain_amd._lib import call, dt, ptr, stream_ptr
     rng = np.random.default_rng(Bg * 1000 + N)
@@ -71,7 +71,7 @@ def test_window_attention_fwd_bwd(dtype, Bg, nG, N, H):
     assert torch.allclose(dtab.cpu().double(), gt, atol=tol * max(1.0, gt.abs().max().item()), rtol=tol)
 
 
-@pytest.mark.parametrize("Bg,nG,N,H", [(6, 3, 49, 3), (8, 2, 49, 6), (2, 1, 96, 12), (4, 2, 24, 24), (3, 3, 1, 6), (2, 1, 128, 3), (82, 41, 49, 3)])
+@pytest.mark.parametrize("Bg,nG,N,H", [(6, 3, 49, 3), (8, 2, 49, 6), (2, 1, 96, 12), (4, 2, 24, 24), (3, 3, 1, 6), (2, 1, 128, 3), (82, 41, 49, 3), (4, 2, 49, 1), (4, 2, 96, 2)])
 def test_window_attention_mfma_fwd_bwd(Bg, nG, N, H):
     """The bf16 MFMA form (evp_window_bias_build -> evp_window_attention_fused_fwd/bwd -> evp_window_bias_reduce) against the
     same float64 formulation as the f32 LDS kernels above, incl. fully masked (padding) groups and NaN-poisoned outputs."""
