@@ -20,12 +20,7 @@ __global__ __launch_bounds__(256) void rows_scale_kernel(const float *__restrict
     const float s = (u && kp < 1.f) ? floorf(kp + u[m / rps]) / kp : 1.f;
     const float4 v = reinterpret_cast<const float4 *>(x)[e];
     float4 o = make_float4(v.x * s, v.y * s, v.z * s, v.w * s);
-    if (lp) {
-      uint2 w;
-      w.x = (uint32_t)f32_to_bf16(o.x) | ((uint32_t)f32_to_bf16(o.y) << 16);
-      w.y = (uint32_t)f32_to_bf16(o.z) | ((uint32_t)f32_to_bf16(o.w) << 16);
-      reinterpret_cast<uint2 *>(lp)[e] = w;
-    }
+    if (lp) reinterpret_cast<uint2 *>(lp)[e] = pack4_bf16(o);
     if (out) {
       if (res) {
         const float4 r = reinterpret_cast<const float4 *>(res)[e];

@@ -55,6 +55,22 @@ __device__ __forceinline__ void st_any(void *p, int dtype, int64_t i, float v) {
   else ((float *)p)[i] = v;
 }
 
+// four elements at once: 16 bytes of f32 or 8 bytes of bf16 (element i of p must be aligned to that)
+__device__ __forceinline__ float4 unpack4_bf16(uint2 u) {
+  return make_float4(__uint_as_float(u.x << 16), __uint_as_float(u.x & 0xFFFF0000u), __uint_as_float(u.y << 16), __uint_as_float(u.y & 0xFFFF0000u));
+}
+__device__ __forceinline__ uint2 pack4_bf16(float4 v) {
+  return make_uint2((uint32_t)f32_to_bf16(v.x) | ((uint32_t)f32_to_bf16(v.y) << 16), (uint32_t)f32_to_bf16(v.z) | ((uint32_t)f32_to_bf16(v.w) << 16));
+}
+__device__ __forceinline__ float4 ld4_any(const void *p, int dtype, int64_t i) {
+  if (dtype == EVP_F32) return *reinterpret_cast<const float4 *>((const float *)p + i);
+  return unpack4_bf16(*reinterpret_cast<const uint2 *>((const bf16_t *)p + i));
+}
+__device__ __forceinline__ void st4_any(void *p, int dtype, int64_t i, float4 v) {
+  if (dtype == EVP_F32) *reinterpret_cast<float4 *>((float *)p + i) = v;
+  else *reinterpret_cast<uint2 *>((bf16_t *)p + i) = pack4_bf16(v);
+}
+
 // ---- wave / block reductions (wave = 64 lanes) --------------------------------------------------------------
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll

@@ -22,6 +22,8 @@ static inline int vpl_for(int D) {
   return r;
 }
 
+__device__ __forceinline__ void add4(float4 &a, float4 b) { a.x += b.x; a.y += b.y; a.z += b.z; a.w += b.w; }
+
 template <int VPL> struct Row {
   float4 v[VPL];
   __device__ __forceinline__ void load(const float *p, int D, int lane) {
@@ -35,24 +37,15 @@ template <int VPL> struct Row {
 #pragma unroll
     for (int i = 0; i < VPL; ++i) {
       const int c = lane + 64 * i;
-      if (c * 4 < D) {
-        const float4 t = *reinterpret_cast<const float4 *>(p + c * 4);
-        v[i].x += t.x; v[i].y += t.y; v[i].z += t.z; v[i].w += t.w;
-      }
+      if (c * 4 < D) add4(v[i], *reinterpret_cast<const float4 *>(p + c * 4));
     }
   }
   __device__ __forceinline__ void load_any(const void *p, int dtype, int64_t off, int D, int lane) {
 #pragma unroll
     for (int i = 0; i < VPL; ++i) {
       const int c = lane + 64 * i;
-      if (c * 4 < D) {
-        if (dtype == EVP_F32) v[i] = *reinterpret_cast<const float4 *>((const float *)p + off + c * 4);
-        else {
-          const uint2 u = *reinterpret_cast<const uint2 *>((const bf16_t *)p + off + c * 4);
-          v[i] = make_float4(__uint_as_float(u.x << 16), __uint_as_float(u.x & 0xFFFF0000u),
-                             __uint_as_float(u.y << 16), __uint_as_float(u.y & 0xFFFF0000u));
-        }
-      } else v[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+      if (c * 4 < D) v[i] = ld4_any(p, dtype, off + c * 4);   // (if / else: as a select, ln_bwd_kernel<2 and 4, false> wait 13 and 23
+      else v[i] = make_float4(0.f, 0.f, 0.f, 0.f);            // more times for their loads, with register copies behind the waits)
     }
   }
   __device__ __forceinline__ float sum(int D, int lane) const {
@@ -74,13 +67,55 @@ template <int VPL> struct Row {
   }
 };
 
-__device__ __forceinline__ void store4_any(void *p, int dtype, int64_t off, float4 v) {
-  if (dtype == EVP_F32) *reinterpret_cast<float4 *>((float *)p + off) = v;
-  else {
-    uint2 u;
-    u.x = (uint32_t)f32_to_bf16(v.x) | ((uint32_t)f32_to_bf16(v.y) << 16);
-    u.y = (uint32_t)f32_to_bf16(v.z) | ((uint32_t)f32_to_bf16(v.w) << 16);
-    *reinterpret_cast<uint2 *>((bf16_t *)p + off) = u;
+// ------------------------------------------------------------------------------------------------ LN arithmetic
+// Written once: the LayerNorm and the patch-embed kernels below compose these and keep only what differs.
+template <int VPL>
+__device__ __forceinline__ void ln_row_stats(const Row<VPL> &row, int D, int lane, float eps, float &mu, float &rs) {
+  mu = row.sum(D, lane) / (float)D;
+  const float var = row.sumsq_centered(mu, D, lane) / (float)D;
+  rs = 1.0f / sqrtf(var + eps);
+}
+__device__ __forceinline__ float4 ln_xhat(float4 x, float mu, float rs) {
+  return make_float4((x.x - mu) * rs, (x.y - mu) * rs, (x.z - mu) * rs, (x.w - mu) * rs);
+}
+// the LayerNorm output z = xhat * gamma + beta
+__device__ __forceinline__ float4 ln_affine(float4 xh, float4 g, float4 b) {
+  return make_float4(xh.x * g.x + b.x, xh.y * g.y + b.y, xh.z * g.z + b.z, xh.w * g.w + b.w);
+}
+// Backward, one chunk of one row; d = the gradient w.r.t. z. A live row adds d * xhat to dgamma and d to dbeta; every row adds its
+// share of s1 = sum t and s2 = sum t * xhat, t = d * gamma (returned).
+__device__ __forceinline__ float4 ln_bwd_step(float4 d, float4 xh, float4 g, bool live, float4 &dg, float4 &db, float &s1, float &s2) {
+  if (live) {
+    add4(dg, make_float4(d.x * xh.x, d.y * xh.y, d.z * xh.z, d.w * xh.w));
+    add4(db, d);
+  }
+  const float4 t = make_float4(d.x * g.x, d.y * g.y, d.z * g.z, d.w * g.w);
+  s1 += (t.x + t.y) + (t.z + t.w);
+  s2 += (t.x * xh.x + t.y * xh.y) + (t.z * xh.z + t.w * xh.w);
+  return t;
+}
+// dx = rstd * (t - m1 - xhat * m2) with the row means m1 = s1 / D, m2 = s2 / D
+__device__ __forceinline__ float4 ln_bwd_out(float4 t, float4 xh, float rs, float m1, float m2) {
+  return make_float4(rs * (t.x - m1 - xh.x * m2), rs * (t.y - m1 - xh.y * m2), rs * (t.z - m1 - xh.z * m2), rs * (t.w - m1 - xh.w * m2));
+}
+// combine the 4 waves' column partials (NP rows of D floats each, sh = [ROWS_PER_BLOCK][NP][D]) through LDS, then one store per
+// block: part[blk][p][D] = sum over the waves of acc[p]
+template <int NP, int VPL>
+__device__ __forceinline__ void ln_flush_partials(const float4 (&acc)[NP][VPL], float *sh, int D, int lane, int wave, float *part) {
+#pragma unroll
+  for (int i = 0; i < VPL; ++i) {
+    const int c = lane + 64 * i;
+    if (c * 4 < D) {
+#pragma unroll
+      for (int p = 0; p < NP; ++p) *reinterpret_cast<float4 *>(sh + (wave * NP + p) * D + c * 4) = acc[p][i];
+    }
+  }
+  __syncthreads();
+  for (int e = threadIdx.x; e < NP * D; e += blockDim.x) {
+    float s = 0.f;
+#pragma unroll
+    for (int w = 0; w < ROWS_PER_BLOCK; ++w) s += sh[w * NP * D + e];
+    part[(int64_t)blockIdx.x * NP * D + e] = s;
   }
 }
 
@@ -95,9 +130,8 @@ __global__ __launch_bounds__(LN_THREADS) void ln_fwd_kernel(const float *x, cons
     row.load(x + r * D, D, lane);
     if (x2) row.add(x2 + r * D, D, lane);
     if (x3) row.add(x3 + r * D, D, lane);
-    const float mu = row.sum(D, lane) / (float)D;
-    const float var = row.sumsq_centered(mu, D, lane) / (float)D;
-    const float rs = 1.0f / sqrtf(var + eps);
+    float mu, rs;
+    ln_row_stats(row, D, lane, eps, mu, rs);
     if (lane == 0) {
       if (mean) mean[r] = mu;
       if (rstd) rstd[r] = rs;
@@ -108,12 +142,7 @@ __global__ __launch_bounds__(LN_THREADS) void ln_fwd_kernel(const float *x, cons
       if (c * 4 < D) {
         const float4 g = *reinterpret_cast<const float4 *>(gamma + c * 4);
         const float4 b = *reinterpret_cast<const float4 *>(beta + c * 4);
-        float4 o;
-        o.x = (row.v[i].x - mu) * rs * g.x + b.x;
-        o.y = (row.v[i].y - mu) * rs * g.y + b.y;
-        o.z = (row.v[i].z - mu) * rs * g.z + b.z;
-        o.w = (row.v[i].w - mu) * rs * g.w + b.w;
-        store4_any(y, y_dtype, r * D + c * 4, o);
+        st4_any(y, y_dtype, r * D + c * 4, ln_affine(ln_xhat(row.v[i], mu, rs), g, b));
       }
     }
   }
@@ -132,11 +161,11 @@ __global__ __launch_bounds__(LN_THREADS) void ln_bwd_kernel(const void *dy, int 
   float *sh = reinterpret_cast<float *>(smem_raw);  // [ROWS_PER_BLOCK][NP][D]
   constexpr int NP = CS ? 3 : 2;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  float4 dg[VPL], db[VPL], dc[CS ? VPL : 1];
+  float4 acc[NP][VPL];                              // dgamma, dbeta and, with CS, the column sums of dx
 #pragma unroll
-  for (int i = 0; i < VPL; ++i) dg[i] = db[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+  for (int p = 0; p < NP; ++p)
 #pragma unroll
-  for (int i = 0; i < (CS ? VPL : 1); ++i) dc[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+    for (int i = 0; i < VPL; ++i) acc[p][i] = make_float4(0.f, 0.f, 0.f, 0.f);
 
   // TWO rows per wave and iteration, every load of both rows (x, dy, the residual-stream gradient, the row statistics) requested
   // before anything is reduced: the one-row form issued x and dy, ran two shuffle reductions, and only then asked for gres -- 6-9
@@ -173,20 +202,9 @@ __global__ __launch_bounds__(LN_THREADS) void ln_bwd_kernel(const void *dy, int 
       if (c * 4 < D) {
         const float4 g = *reinterpret_cast<const float4 *>(gamma + c * 4);
 #pragma unroll
-        for (int k = 0; k < NR; ++k) {
-          float4 xh;
-          xh.x = (xr[k].v[i].x - mu[k]) * rs[k]; xh.y = (xr[k].v[i].y - mu[k]) * rs[k];
-          xh.z = (xr[k].v[i].z - mu[k]) * rs[k]; xh.w = (xr[k].v[i].w - mu[k]) * rs[k];
-          const float4 d = gr[k].v[i];
-          if (live[k]) {
-            dg[i].x += d.x * xh.x; dg[i].y += d.y * xh.y; dg[i].z += d.z * xh.z; dg[i].w += d.w * xh.w;
-            db[i].x += d.x; db[i].y += d.y; db[i].z += d.z; db[i].w += d.w;
-          }
-          float4 t;  // dy * gamma
-          t.x = d.x * g.x; t.y = d.y * g.y; t.z = d.z * g.z; t.w = d.w * g.w;
-          s1[k] += (t.x + t.y) + (t.z + t.w);
-          s2[k] += (t.x * xh.x + t.y * xh.y) + (t.z * xh.z + t.w * xh.w);
-          gr[k].v[i] = t;
+        for (int k = 0; k < NR; ++k) {                 // x -> xhat and dy -> dy * gamma, in place
+          const float4 xh = ln_xhat(xr[k].v[i], mu[k], rs[k]);
+          gr[k].v[i] = ln_bwd_step(gr[k].v[i], xh, g, live[k], acc[0][i], acc[1][i], s1[k], s2[k]);
           xr[k].v[i] = xh;
         }
       }
@@ -206,39 +224,16 @@ __global__ __launch_bounds__(LN_THREADS) void ln_bwd_kernel(const void *dy, int 
       for (int i = 0; i < VPL; ++i) {
         const int c = lane + 64 * i;
         if (c * 4 < D) {
-          float4 o;
-          o.x = rs[k] * (gr[k].v[i].x - m1 - xr[k].v[i].x * m2);
-          o.y = rs[k] * (gr[k].v[i].y - m1 - xr[k].v[i].y * m2);
-          o.z = rs[k] * (gr[k].v[i].z - m1 - xr[k].v[i].z * m2);
-          o.w = rs[k] * (gr[k].v[i].w - m1 - xr[k].v[i].w * m2);
-          if (gres) {
-            const float4 q = qr[k].v[i];
-            o.x += q.x; o.y += q.y; o.z += q.z; o.w += q.w;
-          }
+          float4 o = ln_bwd_out(gr[k].v[i], xr[k].v[i], rs[k], m1, m2);
+          if (gres) add4(o, qr[k].v[i]);
           if (dx) *reinterpret_cast<float4 *>(dx + r * D + c * 4) = o;
-          if (dx_lp) store4_any(dx_lp, EVP_BF16, r * D + c * 4, o);
-          if constexpr (CS) { dc[i].x += o.x; dc[i].y += o.y; dc[i].z += o.z; dc[i].w += o.w; }
+          if (dx_lp) st4_any(dx_lp, EVP_BF16, r * D + c * 4, o);
+          if constexpr (CS) add4(acc[2][i], o);
         }
       }
     }
   }
-  // combine the 4 waves' column partials through LDS, then one store per block
-#pragma unroll
-  for (int i = 0; i < VPL; ++i) {
-    const int c = lane + 64 * i;
-    if (c * 4 < D) {
-      *reinterpret_cast<float4 *>(sh + (wave * NP + 0) * D + c * 4) = dg[i];
-      *reinterpret_cast<float4 *>(sh + (wave * NP + 1) * D + c * 4) = db[i];
-      if constexpr (CS) *reinterpret_cast<float4 *>(sh + (wave * NP + 2) * D + c * 4) = dc[i];
-    }
-  }
-  __syncthreads();
-  for (int e = threadIdx.x; e < NP * D; e += blockDim.x) {
-    float s = 0.f;
-#pragma unroll
-    for (int w = 0; w < ROWS_PER_BLOCK; ++w) s += sh[w * NP * D + e];
-    part[(int64_t)blockIdx.x * NP * D + e] = s;
-  }
+  ln_flush_partials(acc, sh, D, lane, wave, part);
 }
 
 // out0[d] = sum_blk part[blk][0][d], out1[d] = sum_blk part[blk][1][d].
@@ -283,30 +278,25 @@ static inline int ln_grid(int64_t M, int cap = 0) {
 // over a slab of CS_ROWS rows; the 16 row lanes meet in LDS, then ONE f32 atomic per column and block.
 constexpr int CS_ROWS = 256;
 template <typename T>
-__global__ __launch_bounds__(256) void colsum_kernel(const T *x, int64_t M, int N, int64_t ld, float *out) {
-  __shared__ float sh[16][129];
+__device__ __forceinline__ void colsum_body(const T *x, int64_t M, int N, int64_t ld, float *out, int col_block, int row_slab, float (*sh)[129]) {
   const int cc = threadIdx.x & 15, rl = threadIdx.x >> 4;
-  const int n = blockIdx.x * 128 + cc * 8;
-  const int64_t r0 = (int64_t)blockIdx.y * CS_ROWS, r1 = r0 + CS_ROWS < M ? r0 + CS_ROWS : M;
+  const int n = col_block * 128 + cc * 8;
+  const int64_t r0 = (int64_t)row_slab * CS_ROWS, r1 = r0 + CS_ROWS < M ? r0 + CS_ROWS : M;
   float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
   if (n < N) {
     const bool full = n + 7 < N;
     for (int64_t r = r0 + rl; r < r1; r += 16) {
       const T *p = x + r * ld + n;
       if (full) {
+        float4 a, b;
         if constexpr (sizeof(T) == 2) {
           const uint4 u = *reinterpret_cast<const uint4 *>(p);
-          const uint32_t w[4] = {u.x, u.y, u.z, u.w};
-#pragma unroll
-          for (int e = 0; e < 4; ++e) {
-            acc[2 * e] += __uint_as_float(w[e] << 16);
-            acc[2 * e + 1] += __uint_as_float(w[e] & 0xFFFF0000u);
-          }
+          a = unpack4_bf16(make_uint2(u.x, u.y)), b = unpack4_bf16(make_uint2(u.z, u.w));
         } else {
-          const float4 a = *reinterpret_cast<const float4 *>(p), b = *reinterpret_cast<const float4 *>(p + 4);
-          acc[0] += a.x; acc[1] += a.y; acc[2] += a.z; acc[3] += a.w;
-          acc[4] += b.x; acc[5] += b.y; acc[6] += b.z; acc[7] += b.w;
+          a = *reinterpret_cast<const float4 *>(p), b = *reinterpret_cast<const float4 *>(p + 4);
         }
+        acc[0] += a.x; acc[1] += a.y; acc[2] += a.z; acc[3] += a.w;
+        acc[4] += b.x; acc[5] += b.y; acc[6] += b.z; acc[7] += b.w;
       } else {
         for (int e = 0; e < 8 && n + e < N; ++e) acc[e] += ElemIO<T>::ld(p + e);
       }
@@ -320,8 +310,13 @@ __global__ __launch_bounds__(256) void colsum_kernel(const T *x, int64_t M, int 
     float t = 0.f;
 #pragma unroll
     for (int i = 0; i < 16; ++i) t += sh[i][c];
-    if (blockIdx.x * 128 + c < N) atomicAdd(out + blockIdx.x * 128 + c, t);
+    if (col_block * 128 + c < N) atomicAdd(out + col_block * 128 + c, t);
   }
+}
+template <typename T>
+__global__ __launch_bounds__(256) void colsum_kernel(const T *x, int64_t M, int N, int64_t ld, float *out) {
+  __shared__ float sh[16][129];
+  colsum_body(x, M, N, ld, out, blockIdx.x, blockIdx.y, sh);
 }
 
 // grouped form: many independent column sums in one launch (the deferred bias gradients of a whole step).
@@ -331,49 +326,12 @@ __global__ __launch_bounds__(256) void colsum_grouped_kernel(const ColsumProblem
   __shared__ float sh[16][129];
   const ColsumItem it = items[blockIdx.x];
   const ColsumProblem g = probs[it.prob];
-  const int cc = threadIdx.x & 15, rl = threadIdx.x >> 4;
-  const int n = it.col_block * 128 + cc * 8;
-  const int64_t r0 = (int64_t)it.row_slab * CS_ROWS, r1 = r0 + CS_ROWS < g.M ? r0 + CS_ROWS : g.M;
-  float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-  if (n < g.N) {
-    const bool full = n + 7 < g.N;
-    for (int64_t r = r0 + rl; r < r1; r += 16) {
-      if (g.dtype == EVP_BF16) {
-        const bf16_t *p = (const bf16_t *)g.x + r * g.ld + n;
-        if (full) {
-          const uint4 u = *reinterpret_cast<const uint4 *>(p);
-          const uint32_t w[4] = {u.x, u.y, u.z, u.w};
-#pragma unroll
-          for (int e = 0; e < 4; ++e) {
-            acc[2 * e] += __uint_as_float(w[e] << 16);
-            acc[2 * e + 1] += __uint_as_float(w[e] & 0xFFFF0000u);
-          }
-        } else
-          for (int e = 0; e < 8 && n + e < g.N; ++e) acc[e] += bf16_to_f32(p[e]);
-      } else {
-        const float *p = (const float *)g.x + r * g.ld + n;
-        if (full) {
-          const float4 a = *reinterpret_cast<const float4 *>(p), b = *reinterpret_cast<const float4 *>(p + 4);
-          acc[0] += a.x; acc[1] += a.y; acc[2] += a.z; acc[3] += a.w;
-          acc[4] += b.x; acc[5] += b.y; acc[6] += b.z; acc[7] += b.w;
-        } else
-          for (int e = 0; e < 8 && n + e < g.N; ++e) acc[e] += p[e];
-      }
-    }
-  }
-#pragma unroll
-  for (int e = 0; e < 8; ++e) sh[rl][cc * 8 + e] = acc[e];
-  __syncthreads();
-  if (threadIdx.x < 128) {
-    const int c = threadIdx.x;
-    float t = 0.f;
-#pragma unroll
-    for (int i = 0; i < 16; ++i) t += sh[i][c];
-    if (it.col_block * 128 + c < g.N) atomicAdd(g.out + it.col_block * 128 + c, t);
-  }
+  if (g.dtype == EVP_BF16) colsum_body((const bf16_t *)g.x, g.M, g.N, g.ld, g.out, it.col_block, it.row_slab, sh);
+  else colsum_body((const float *)g.x, g.M, g.N, g.ld, g.out, it.col_block, it.row_slab, sh);
 }
 
 // ------------------------------------------------------------------------------------------------ patch-embed post-op
+// out = GELU(LayerNorm(y)) + pos[token]: the LayerNorm kernels above, one row per iteration, plus the GELU and the position add
 template <int VPL>
 __global__ __launch_bounds__(LN_THREADS) void embed_post_fwd_kernel(const float *y, const float *gamma, const float *beta,
                                                              const float *pos, const int64_t *ids_keep, int64_t M,
@@ -383,9 +341,8 @@ __global__ __launch_bounds__(LN_THREADS) void embed_post_fwd_kernel(const float 
   for (int64_t r = (int64_t)blockIdx.x * ROWS_PER_BLOCK + wave; r < M; r += (int64_t)gridDim.x * ROWS_PER_BLOCK) {
     Row<VPL> row;
     row.load(y + r * D, D, lane);
-    const float mu = row.sum(D, lane) / (float)D;
-    const float var = row.sumsq_centered(mu, D, lane) / (float)D;
-    const float rs = 1.0f / sqrtf(var + eps);
+    float mu, rs;
+    ln_row_stats(row, D, lane, eps, mu, rs);
     if (lane == 0) { mean[r] = mu; rstd[r] = rs; }
     const int64_t tok = ids_keep ? ids_keep[r] : (r % L);
     const float *pr = pos ? pos + tok * D : nullptr;
@@ -396,12 +353,8 @@ __global__ __launch_bounds__(LN_THREADS) void embed_post_fwd_kernel(const float 
         const float4 g = *reinterpret_cast<const float4 *>(gamma + c * 4);
         const float4 b = *reinterpret_cast<const float4 *>(beta + c * 4);
         const float4 pe = pr ? *reinterpret_cast<const float4 *>(pr + c * 4) : make_float4(0.f, 0.f, 0.f, 0.f);
-        float4 o;
-        o.x = gelu_f((row.v[i].x - mu) * rs * g.x + b.x) + pe.x;
-        o.y = gelu_f((row.v[i].y - mu) * rs * g.y + b.y) + pe.y;
-        o.z = gelu_f((row.v[i].z - mu) * rs * g.z + b.z) + pe.z;
-        o.w = gelu_f((row.v[i].w - mu) * rs * g.w + b.w) + pe.w;
-        *reinterpret_cast<float4 *>(out + r * D + c * 4) = o;
+        const float4 z = ln_affine(ln_xhat(row.v[i], mu, rs), g, b);
+        *reinterpret_cast<float4 *>(out + r * D + c * 4) = make_float4(gelu_f(z.x) + pe.x, gelu_f(z.y) + pe.y, gelu_f(z.z) + pe.z, gelu_f(z.w) + pe.w);
       }
     }
   }
@@ -414,9 +367,9 @@ __global__ __launch_bounds__(LN_THREADS) void embed_post_bwd_kernel(const float 
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
   float *sh = reinterpret_cast<float *>(smem_raw);
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  float4 dg[VPL], db[VPL];
+  float4 acc[2][VPL];                               // dgamma, dbeta
 #pragma unroll
-  for (int i = 0; i < VPL; ++i) dg[i] = db[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+  for (int i = 0; i < VPL; ++i) acc[0][i] = acc[1][i] = make_float4(0.f, 0.f, 0.f, 0.f);
   for (int64_t r = (int64_t)blockIdx.x * ROWS_PER_BLOCK + wave; r < M; r += (int64_t)gridDim.x * ROWS_PER_BLOCK) {
     Row<VPL> xr, gr;
     xr.load(y + r * D, D, lane);
@@ -429,21 +382,10 @@ __global__ __launch_bounds__(LN_THREADS) void embed_post_bwd_kernel(const float 
       if (c * 4 < D) {
         const float4 g = *reinterpret_cast<const float4 *>(gamma + c * 4);
         const float4 b = *reinterpret_cast<const float4 *>(beta + c * 4);
-        float4 xh;
-        xh.x = (xr.v[i].x - mu) * rs; xh.y = (xr.v[i].y - mu) * rs;
-        xh.z = (xr.v[i].z - mu) * rs; xh.w = (xr.v[i].w - mu) * rs;
-        float4 d;  // gradient w.r.t. the LayerNorm output z = xh*gamma+beta
-        d.x = gr.v[i].x * dgelu_f(xh.x * g.x + b.x);
-        d.y = gr.v[i].y * dgelu_f(xh.y * g.y + b.y);
-        d.z = gr.v[i].z * dgelu_f(xh.z * g.z + b.z);
-        d.w = gr.v[i].w * dgelu_f(xh.w * g.w + b.w);
-        dg[i].x += d.x * xh.x; dg[i].y += d.y * xh.y; dg[i].z += d.z * xh.z; dg[i].w += d.w * xh.w;
-        db[i].x += d.x; db[i].y += d.y; db[i].z += d.z; db[i].w += d.w;
-        float4 t;
-        t.x = d.x * g.x; t.y = d.y * g.y; t.z = d.z * g.z; t.w = d.w * g.w;
-        s1 += (t.x + t.y) + (t.z + t.w);
-        s2 += (t.x * xh.x + t.y * xh.y) + (t.z * xh.z + t.w * xh.w);
-        gr.v[i] = t;
+        const float4 xh = ln_xhat(xr.v[i], mu, rs), z = ln_affine(xh, g, b), gi = gr.v[i];
+        // gradient w.r.t. the LayerNorm output z = xh*gamma+beta
+        const float4 d = make_float4(gi.x * dgelu_f(z.x), gi.y * dgelu_f(z.y), gi.z * dgelu_f(z.z), gi.w * dgelu_f(z.w));
+        gr.v[i] = ln_bwd_step(d, xh, g, true, acc[0][i], acc[1][i], s1, s2);
         xr.v[i] = xh;
       }
     }
@@ -452,52 +394,91 @@ __global__ __launch_bounds__(LN_THREADS) void embed_post_bwd_kernel(const float 
 #pragma unroll
     for (int i = 0; i < VPL; ++i) {
       const int c = lane + 64 * i;
-      if (c * 4 < D) {
-        float4 o;
-        o.x = rs * (gr.v[i].x - s1 - xr.v[i].x * s2);
-        o.y = rs * (gr.v[i].y - s1 - xr.v[i].y * s2);
-        o.z = rs * (gr.v[i].z - s1 - xr.v[i].z * s2);
-        o.w = rs * (gr.v[i].w - s1 - xr.v[i].w * s2);
-        store4_any(dy, dy_dtype, r * D + c * 4, o);
-      }
+      if (c * 4 < D) st4_any(dy, dy_dtype, r * D + c * 4, ln_bwd_out(gr.v[i], xr.v[i], rs, s1, s2));
     }
   }
-#pragma unroll
-  for (int i = 0; i < VPL; ++i) {
-    const int c = lane + 64 * i;
-    if (c * 4 < D) {
-      *reinterpret_cast<float4 *>(sh + (wave * 2 + 0) * D + c * 4) = dg[i];
-      *reinterpret_cast<float4 *>(sh + (wave * 2 + 1) * D + c * 4) = db[i];
-    }
-  }
-  __syncthreads();
-  for (int e = threadIdx.x; e < 2 * D; e += blockDim.x) {
-    float s = 0.f;
-#pragma unroll
-    for (int w = 0; w < ROWS_PER_BLOCK; ++w) s += sh[w * 2 * D + e];
-    part[(int64_t)blockIdx.x * 2 * D + e] = s;
-  }
+  ln_flush_partials(acc, sh, D, lane, wave, part);
 }
 
 // ------------------------------------------------------------------------------------------------ BatchNorm over rows
+// Every pass in two widths W: 1, one element per lane, and 4 (C % 4 == 0 and 16-byte aligned tensors), 16-byte (f32) / 8-byte (bf16)
+// accesses. The per-slab passes run 256 / W column groups x W row lanes over one slab of BN_ROWS rows; at W = 4 the row lanes meet
+// in LDS.
 constexpr int BN_ROWS = 64;
+template <int W> __device__ __forceinline__ void ldw_any(const void *p, int dtype, int64_t i, float (&v)[W]) {
+  static_assert(W == 1 || W == 4, "BatchNorm widths");
+  if constexpr (W == 4) {
+    const float4 t = ld4_any(p, dtype, i);
+    v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
+  } else v[0] = ld_any(p, dtype, i);
+}
+template <int W> __device__ __forceinline__ void stw_any(void *p, int dtype, int64_t i, const float (&v)[W]) {
+  if constexpr (W == 4) st4_any(p, dtype, i, make_float4(v[0], v[1], v[2], v[3]));
+  else st_any(p, dtype, i, v[0]);
+}
+// dy' = the upstream gradient behind the ReLU (zero where the output y is not positive)
+template <int W> __device__ __forceinline__ void bn_load_dy(const void *dy, const void *y, int dtype, int64_t i, int relu, float (&d)[W]) {
+  ldw_any<W>(dy, dtype, i, d);
+  if (relu) {
+    float yv[W];
+    ldw_any<W>(y, dtype, i, yv);
+#pragma unroll
+    for (int j = 0; j < W; ++j)
+      if (!(yv[j] > 0.f)) d[j] = 0.f;
+  }
+}
+
 // Welford per (slab, column): part[slab][0][C] = mean, part[slab][1][C] = M2, count = rows in slab
+template <int W>
 __global__ __launch_bounds__(256) void bn_stats_partial(const void *x, int dtype, int64_t R, int C, float *part) {
-  const int c = blockIdx.x * 256 + threadIdx.x;
-  if (c >= C) return;
+  constexpr int NG = 256 / W;
+  const int cg = threadIdx.x % NG, rl = threadIdx.x / NG;
+  const int c = blockIdx.x * 256 + cg * W;
   const int64_t r0 = (int64_t)blockIdx.y * BN_ROWS;
   const int64_t r1 = r0 + BN_ROWS < R ? r0 + BN_ROWS : R;
-  float mean = 0.f, m2 = 0.f;
+  float mean[W], m2[W];
+#pragma unroll
+  for (int j = 0; j < W; ++j) mean[j] = m2[j] = 0.f;
   int n = 0;
-  for (int64_t r = r0; r < r1; ++r) {
-    const float v = ld_any(x, dtype, r * C + c);
-    ++n;
-    const float d = v - mean;
-    mean += d / (float)n;
-    m2 += d * (v - mean);
+  if (c < C)
+    for (int64_t r = r0 + rl; r < r1; r += W) {
+      float v[W];
+      ldw_any<W>(x, dtype, r * C + c, v);
+      ++n;
+#pragma unroll
+      for (int j = 0; j < W; ++j) {
+        const float d = v[j] - mean[j];
+        if constexpr (W == 1) mean[j] += d / (float)n;   // pins the parent's rounding: width 1 divides, width 4 multiplies by 1 / n
+        else mean[j] += d * (1.0f / (float)n);
+        m2[j] += d * (v[j] - mean[j]);
+      }
+    }
+  if constexpr (W == 1) {
+    if (c < C) {
+      part[((int64_t)blockIdx.y * 2 + 0) * C + c] = mean[0];
+      part[((int64_t)blockIdx.y * 2 + 1) * C + c] = m2[0];
+    }
+  } else {
+    __shared__ float sh[3][W][260];
+#pragma unroll
+    for (int j = 0; j < W; ++j) { sh[0][rl][cg * W + j] = (float)n; sh[1][rl][cg * W + j] = mean[j]; sh[2][rl][cg * W + j] = m2[j]; }
+    __syncthreads();
+    const int cc = threadIdx.x;                      // one column per thread for the combine
+    if (blockIdx.x * 256 + cc < C) {
+      float nn = sh[0][0][cc], mu = sh[1][0][cc], q = sh[2][0][cc];
+      for (int i = 1; i < W; ++i) {
+        const float nb = sh[0][i][cc];
+        if (nb > 0.f) {
+          const float delta = sh[1][i][cc] - mu, tot = nn + nb;
+          mu += delta * nb / tot;
+          q += sh[2][i][cc] + delta * delta * nn * nb / tot;
+          nn = tot;
+        }
+      }
+      part[((int64_t)blockIdx.y * 2 + 0) * C + blockIdx.x * 256 + cc] = mu;
+      part[((int64_t)blockIdx.y * 2 + 1) * C + blockIdx.x * 256 + cc] = q;
+    }
   }
-  part[((int64_t)blockIdx.y * 2 + 0) * C + c] = mean;
-  part[((int64_t)blockIdx.y * 2 + 1) * C + c] = m2;
 }
 // 1024 threads = 64 columns x 16 slab groups: each thread folds every 16th slab (Chan's pairwise update, in double), the 16 partial
 // (n, mean, M2) triples of a column then meet in LDS. (One thread per column walking all R / 64 slabs serially took 68 us at
@@ -537,33 +518,75 @@ __global__ __launch_bounds__(1024) void bn_stats_finalize(const float *part, int
     if (running_var) running_var[c] = (1.f - momentum) * running_var[c] + momentum * (float)(m2 / (n > 1.0 ? n - 1.0 : 1.0));
   }
 }
+template <int W>
 __global__ __launch_bounds__(256) void bn_apply(const void *x, int dtype, int64_t total, int C, const float *gamma,
                                                 const float *beta, const float *mean, const float *invstd, int relu, void *y) {
-  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+  for (int64_t iw = (int64_t)blockIdx.x * 256 + threadIdx.x; iw < total / W; iw += (int64_t)gridDim.x * 256) {
+    const int64_t i = iw * W;
     const int c = (int)(i % C);
-    float v = (ld_any(x, dtype, i) - mean[c]) * invstd[c];
-    if (gamma) v = v * gamma[c] + beta[c];
-    if (relu) v = fmaxf(v, 0.f);
-    st_any(y, dtype, i, v);
+    float o[W], mu[W], is[W];
+    ldw_any<W>(x, dtype, i, o);
+    ldw_any<W>(mean, EVP_F32, c, mu);
+    ldw_any<W>(invstd, EVP_F32, c, is);
+#pragma unroll
+    for (int j = 0; j < W; ++j) o[j] = (o[j] - mu[j]) * is[j];
+    if (gamma) {
+      float g[W], b[W];
+      ldw_any<W>(gamma, EVP_F32, c, g);
+      ldw_any<W>(beta, EVP_F32, c, b);
+#pragma unroll
+      for (int j = 0; j < W; ++j) o[j] = o[j] * g[j] + b[j];
+    }
+    if (relu) {
+#pragma unroll
+      for (int j = 0; j < W; ++j) o[j] = fmaxf(o[j], 0.f);
+    }
+    stw_any<W>(y, dtype, i, o);
   }
 }
 // part[slab][0][C] = sum dy', part[slab][1][C] = sum dy' * xhat
+template <int W>
 __global__ __launch_bounds__(256) void bn_bwd_partial(const void *dy, const void *x, const void *y, int dtype, int64_t R, int C,
                                                       const float *mean, const float *invstd, int relu, float *part) {
-  const int c = blockIdx.x * 256 + threadIdx.x;
-  if (c >= C) return;
+  constexpr int NG = 256 / W;
+  const int cg = threadIdx.x % NG, rl = threadIdx.x / NG;
+  const int c = blockIdx.x * 256 + cg * W;
   const int64_t r0 = (int64_t)blockIdx.y * BN_ROWS;
   const int64_t r1 = r0 + BN_ROWS < R ? r0 + BN_ROWS : R;
-  const float mu = mean[c], is = invstd[c];
-  float s0 = 0.f, s1 = 0.f;
-  for (int64_t r = r0; r < r1; ++r) {
-    float d = ld_any(dy, dtype, r * C + c);
-    if (relu && !(ld_any(y, dtype, r * C + c) > 0.f)) d = 0.f;
-    s0 += d;
-    s1 += d * (ld_any(x, dtype, r * C + c) - mu) * is;
+  float s0[W], s1[W];
+#pragma unroll
+  for (int j = 0; j < W; ++j) s0[j] = s1[j] = 0.f;
+  if (c < C) {
+    float mu[W], is[W];
+    ldw_any<W>(mean, EVP_F32, c, mu);
+    ldw_any<W>(invstd, EVP_F32, c, is);
+    for (int64_t r = r0 + rl; r < r1; r += W) {
+      float d[W], xv[W];
+      bn_load_dy<W>(dy, y, dtype, r * C + c, relu, d);
+      ldw_any<W>(x, dtype, r * C + c, xv);
+#pragma unroll
+      for (int j = 0; j < W; ++j) {
+        s0[j] += d[j];
+        s1[j] += d[j] * (xv[j] - mu[j]) * is[j];
+      }
+    }
   }
-  part[((int64_t)blockIdx.y * 2 + 0) * C + c] = s0;
-  part[((int64_t)blockIdx.y * 2 + 1) * C + c] = s1;
+  if constexpr (W == 1) {
+    if (c < C) {
+      part[((int64_t)blockIdx.y * 2 + 0) * C + c] = s0[0];
+      part[((int64_t)blockIdx.y * 2 + 1) * C + c] = s1[0];
+    }
+  } else {                                           // pins the parent's rounding: the four row lanes add pairwise
+    __shared__ float sh[2][W][260];
+#pragma unroll
+    for (int j = 0; j < W; ++j) { sh[0][rl][cg * W + j] = s0[j]; sh[1][rl][cg * W + j] = s1[j]; }
+    __syncthreads();
+    const int cc = threadIdx.x;
+    if (blockIdx.x * 256 + cc < C) {
+      part[((int64_t)blockIdx.y * 2 + 0) * C + blockIdx.x * 256 + cc] = (sh[0][0][cc] + sh[0][1][cc]) + (sh[0][2][cc] + sh[0][3][cc]);
+      part[((int64_t)blockIdx.y * 2 + 1) * C + blockIdx.x * 256 + cc] = (sh[1][0][cc] + sh[1][1][cc]) + (sh[1][2][cc] + sh[1][3][cc]);
+    }
+  }
 }
 __global__ __launch_bounds__(1024) void bn_bwd_finalize(const float *part, int nslab, int C, float *sum_dy, float *sum_dy_xhat) {
   __shared__ float sh[2][16][65];
@@ -583,165 +606,29 @@ __global__ __launch_bounds__(1024) void bn_bwd_finalize(const float *part, int n
     sum_dy_xhat[c] = b;
   }
 }
+template <int W>
 __global__ __launch_bounds__(256) void bn_bwd_apply(const void *dy, const void *x, const void *y, int dtype, int64_t R, int C,
                                                     const float *gamma, const float *mean, const float *invstd, int relu,
                                                     const float *sum_dy, const float *sum_dy_xhat, void *dx) {
   const int64_t total = R * C;
   const float invR = 1.0f / (float)R;
-  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+  for (int64_t iw = (int64_t)blockIdx.x * 256 + threadIdx.x; iw < total / W; iw += (int64_t)gridDim.x * 256) {
+    const int64_t i = iw * W;
     const int c = (int)(i % C);
-    float d = ld_any(dy, dtype, i);
-    if (relu && !(ld_any(y, dtype, i) > 0.f)) d = 0.f;
-    const float xh = (ld_any(x, dtype, i) - mean[c]) * invstd[c];
-    const float g = gamma ? gamma[c] : 1.f;
-    st_any(dx, dtype, i, g * invstd[c] * (d - sum_dy[c] * invR - xh * sum_dy_xhat[c] * invR));
-  }
-}
-
-// ---- 4-column vector forms (C % 4 == 0): 16-byte (f32) / 8-byte (bf16) accesses instead of one element per lane; a block is 64
-// column groups x 4 row lanes over one slab of BN_ROWS rows, the row lanes meet in LDS -------------------------------------------
-__device__ __forceinline__ float4 ld4_any(const void *p, int dtype, int64_t i) {
-  if (dtype == EVP_BF16) {
-    const uint2 u = *reinterpret_cast<const uint2 *>(reinterpret_cast<const bf16_t *>(p) + i);
-    return make_float4(__uint_as_float(u.x << 16), __uint_as_float(u.x & 0xFFFF0000u), __uint_as_float(u.y << 16), __uint_as_float(u.y & 0xFFFF0000u));
-  }
-  return *reinterpret_cast<const float4 *>(reinterpret_cast<const float *>(p) + i);
-}
-__device__ __forceinline__ void st4_any(void *p, int dtype, int64_t i, float4 v) {
-  if (dtype == EVP_BF16) {
-    uint2 u;
-    u.x = (uint32_t)f32_to_bf16(v.x) | ((uint32_t)f32_to_bf16(v.y) << 16);
-    u.y = (uint32_t)f32_to_bf16(v.z) | ((uint32_t)f32_to_bf16(v.w) << 16);
-    *reinterpret_cast<uint2 *>(reinterpret_cast<bf16_t *>(p) + i) = u;
-  } else {
-    *reinterpret_cast<float4 *>(reinterpret_cast<float *>(p) + i) = v;
-  }
-}
-__global__ __launch_bounds__(256) void bn_stats_partial_v4(const void *x, int dtype, int64_t R, int C, float *part) {
-  __shared__ float sh[3][4][260];
-  const int cg = threadIdx.x & 63, rl = threadIdx.x >> 6;
-  const int c = blockIdx.x * 256 + cg * 4;
-  const int64_t r0 = (int64_t)blockIdx.y * BN_ROWS;
-  const int64_t r1 = r0 + BN_ROWS < R ? r0 + BN_ROWS : R;
-  float mean[4] = {0.f, 0.f, 0.f, 0.f}, m2[4] = {0.f, 0.f, 0.f, 0.f};
-  int n = 0;
-  if (c < C)
-    for (int64_t r = r0 + rl; r < r1; r += 4) {
-      const float4 v4 = ld4_any(x, dtype, r * C + c);
-      const float v[4] = {v4.x, v4.y, v4.z, v4.w};
-      ++n;
-      const float inv = 1.0f / (float)n;
+    float d[W], xv[W], mu[W], is[W], s0[W], s1[W], g[W], o[W];
+    bn_load_dy<W>(dy, y, dtype, i, relu, d);
+    ldw_any<W>(x, dtype, i, xv);
+    ldw_any<W>(mean, EVP_F32, c, mu);
+    ldw_any<W>(invstd, EVP_F32, c, is);
+    ldw_any<W>(sum_dy, EVP_F32, c, s0);
+    ldw_any<W>(sum_dy_xhat, EVP_F32, c, s1);
+    if (gamma) ldw_any<W>(gamma, EVP_F32, c, g);
 #pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const float d = v[j] - mean[j];
-        mean[j] += d * inv;
-        m2[j] += d * (v[j] - mean[j]);
-      }
+    for (int j = 0; j < W; ++j) {
+      const float xh = (xv[j] - mu[j]) * is[j];
+      o[j] = (gamma ? g[j] : 1.f) * is[j] * (d[j] - s0[j] * invR - xh * s1[j] * invR);
     }
-#pragma unroll
-  for (int j = 0; j < 4; ++j) { sh[0][rl][cg * 4 + j] = (float)n; sh[1][rl][cg * 4 + j] = mean[j]; sh[2][rl][cg * 4 + j] = m2[j]; }
-  __syncthreads();
-  const int cc = threadIdx.x;                      // one column per thread for the combine
-  if (blockIdx.x * 256 + cc < C) {
-    float nn = sh[0][0][cc], mu = sh[1][0][cc], q = sh[2][0][cc];
-    for (int i = 1; i < 4; ++i) {
-      const float nb = sh[0][i][cc];
-      if (nb > 0.f) {
-        const float delta = sh[1][i][cc] - mu, tot = nn + nb;
-        mu += delta * nb / tot;
-        q += sh[2][i][cc] + delta * delta * nn * nb / tot;
-        nn = tot;
-      }
-    }
-    part[((int64_t)blockIdx.y * 2 + 0) * C + blockIdx.x * 256 + cc] = mu;
-    part[((int64_t)blockIdx.y * 2 + 1) * C + blockIdx.x * 256 + cc] = q;
-  }
-}
-__global__ __launch_bounds__(256) void bn_bwd_partial_v4(const void *dy, const void *x, const void *y, int dtype, int64_t R, int C,
-                                                         const float *mean, const float *invstd, int relu, float *part) {
-  __shared__ float sh[2][4][260];
-  const int cg = threadIdx.x & 63, rl = threadIdx.x >> 6;
-  const int c = blockIdx.x * 256 + cg * 4;
-  const int64_t r0 = (int64_t)blockIdx.y * BN_ROWS;
-  const int64_t r1 = r0 + BN_ROWS < R ? r0 + BN_ROWS : R;
-  float s0[4] = {0.f, 0.f, 0.f, 0.f}, s1[4] = {0.f, 0.f, 0.f, 0.f};
-  if (c < C) {
-    const float4 mu = *reinterpret_cast<const float4 *>(mean + c), is = *reinterpret_cast<const float4 *>(invstd + c);
-    const float mua[4] = {mu.x, mu.y, mu.z, mu.w}, isa[4] = {is.x, is.y, is.z, is.w};
-    for (int64_t r = r0 + rl; r < r1; r += 4) {
-      const float4 d4 = ld4_any(dy, dtype, r * C + c), x4 = ld4_any(x, dtype, r * C + c);
-      float d[4] = {d4.x, d4.y, d4.z, d4.w};
-      const float xv[4] = {x4.x, x4.y, x4.z, x4.w};
-      if (relu) {
-        const float4 y4 = ld4_any(y, dtype, r * C + c);
-        const float yv[4] = {y4.x, y4.y, y4.z, y4.w};
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-          if (!(yv[j] > 0.f)) d[j] = 0.f;
-      }
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        s0[j] += d[j];
-        s1[j] += d[j] * (xv[j] - mua[j]) * isa[j];
-      }
-    }
-  }
-#pragma unroll
-  for (int j = 0; j < 4; ++j) { sh[0][rl][cg * 4 + j] = s0[j]; sh[1][rl][cg * 4 + j] = s1[j]; }
-  __syncthreads();
-  const int cc = threadIdx.x;
-  if (blockIdx.x * 256 + cc < C) {
-    part[((int64_t)blockIdx.y * 2 + 0) * C + blockIdx.x * 256 + cc] = (sh[0][0][cc] + sh[0][1][cc]) + (sh[0][2][cc] + sh[0][3][cc]);
-    part[((int64_t)blockIdx.y * 2 + 1) * C + blockIdx.x * 256 + cc] = (sh[1][0][cc] + sh[1][1][cc]) + (sh[1][2][cc] + sh[1][3][cc]);
-  }
-}
-__global__ __launch_bounds__(256) void bn_apply_v4(const void *x, int dtype, int64_t total4, int C, const float *gamma, const float *beta,
-                                                   const float *mean, const float *invstd, int relu, void *y) {
-  for (int64_t i4 = (int64_t)blockIdx.x * 256 + threadIdx.x; i4 < total4; i4 += (int64_t)gridDim.x * 256) {
-    const int64_t i = i4 * 4;
-    const int c = (int)(i % C);
-    const float4 v = ld4_any(x, dtype, i), mu = *reinterpret_cast<const float4 *>(mean + c), is = *reinterpret_cast<const float4 *>(invstd + c);
-    float o[4] = {(v.x - mu.x) * is.x, (v.y - mu.y) * is.y, (v.z - mu.z) * is.z, (v.w - mu.w) * is.w};
-    if (gamma) {
-      const float4 g = *reinterpret_cast<const float4 *>(gamma + c), b = *reinterpret_cast<const float4 *>(beta + c);
-      o[0] = o[0] * g.x + b.x; o[1] = o[1] * g.y + b.y; o[2] = o[2] * g.z + b.z; o[3] = o[3] * g.w + b.w;
-    }
-    if (relu) {
-#pragma unroll
-      for (int j = 0; j < 4; ++j) o[j] = fmaxf(o[j], 0.f);
-    }
-    st4_any(y, dtype, i, make_float4(o[0], o[1], o[2], o[3]));
-  }
-}
-__global__ __launch_bounds__(256) void bn_bwd_apply_v4(const void *dy, const void *x, const void *y, int dtype, int64_t total4, int64_t R, int C,
-                                                       const float *gamma, const float *mean, const float *invstd, int relu,
-                                                       const float *sum_dy, const float *sum_dy_xhat, void *dx) {
-  const float invR = 1.0f / (float)R;
-  for (int64_t i4 = (int64_t)blockIdx.x * 256 + threadIdx.x; i4 < total4; i4 += (int64_t)gridDim.x * 256) {
-    const int64_t i = i4 * 4;
-    const int c = (int)(i % C);
-    const float4 d4 = ld4_any(dy, dtype, i), x4 = ld4_any(x, dtype, i);
-    float d[4] = {d4.x, d4.y, d4.z, d4.w};
-    const float xv[4] = {x4.x, x4.y, x4.z, x4.w};
-    if (relu) {
-      const float4 y4 = ld4_any(y, dtype, i);
-      const float yv[4] = {y4.x, y4.y, y4.z, y4.w};
-#pragma unroll
-      for (int j = 0; j < 4; ++j)
-        if (!(yv[j] > 0.f)) d[j] = 0.f;
-    }
-    const float4 is4 = *reinterpret_cast<const float4 *>(invstd + c), mu4 = *reinterpret_cast<const float4 *>(mean + c);
-    const float4 s04 = *reinterpret_cast<const float4 *>(sum_dy + c), s14 = *reinterpret_cast<const float4 *>(sum_dy_xhat + c);
-    const float4 g4 = gamma ? *reinterpret_cast<const float4 *>(gamma + c) : make_float4(1.f, 1.f, 1.f, 1.f);
-    const float isa[4] = {is4.x, is4.y, is4.z, is4.w}, mua[4] = {mu4.x, mu4.y, mu4.z, mu4.w};
-    const float s0a[4] = {s04.x, s04.y, s04.z, s04.w}, s1a[4] = {s14.x, s14.y, s14.z, s14.w}, ga[4] = {g4.x, g4.y, g4.z, g4.w};
-    float o[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const float xh = (xv[j] - mua[j]) * isa[j];
-      o[j] = ga[j] * isa[j] * (d[j] - s0a[j] * invR - xh * s1a[j] * invR);
-    }
-    st4_any(dx, dtype, i, make_float4(o[0], o[1], o[2], o[3]));
+    stw_any<W>(dx, dtype, i, o);
   }
 }
 
@@ -756,10 +643,32 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_v4(const void *dy, const voi
     default: { constexpr int V = 16; CALL; } break;             \
   }
 
+// what every row kernel needs of its shape
+static inline bool ln_shape_ok(int64_t M, int D) { return M > 0 && D > 0 && D % 4 == 0 && D <= 4096; }
+
+// A backward launch: `lds` bytes of dynamic LDS (above 48 KiB the kernel's limit has to be raised first), then, with dgamma or dbeta
+// given, the reduction of the per-block partial rows workspace[grid][2][D]. Both NULL: the caller reduces them itself (deferred, grouped).
+template <typename... P, typename... A>
+static int ln_bwd_launch(const char *entry, void (*kernel)(P...), int grid, size_t lds, hipStream_t s, float *workspace, int D, float *dgamma,
+                         float *dbeta, A... args) {
+  if (lds > 48 * 1024) {
+    hipError_t ea = hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    EVP_CHECK_ARG(ea == hipSuccess, EVP_ELAUNCH, "%s: hipFuncSetAttribute(%zu) failed: %s", entry, lds, hipGetErrorString(ea));
+  }
+  hipLaunchKernelGGL(kernel, dim3(grid), dim3(LN_THREADS), lds, s, args...);
+  EVP_CHECK_LAUNCH(entry);
+  if (dgamma || dbeta) {
+    hipLaunchKernelGGL(ln_bwd_finalize, dim3((2 * D + 63) / 64), dim3(1024), 0, s, workspace, grid, D, dgamma, dbeta);
+    hipError_t ef = hipGetLastError();
+    EVP_CHECK_ARG(ef == hipSuccess, EVP_ELAUNCH, "%s(finalize): launch failed: %s", entry, hipGetErrorString(ef));
+  }
+  return EVP_OK;
+}
+
 extern "C" int evp_layernorm_fwd(const float *x, const float *x2, const float *x3, const float *gamma, const float *beta,
                                  int64_t M, int D, float eps, void *y, int y_dtype, float *mean, float *rstd, void *stream) {
   EVP_CHECK_ARG(x && gamma && beta && y, EVP_EINVAL, "evp_layernorm_fwd: null pointer");
-  EVP_CHECK_ARG(M > 0 && D > 0 && D % 4 == 0 && D <= 4096, EVP_ESHAPE, "evp_layernorm_fwd: need M>0, D%%4==0, D<=4096 (M=%lld D=%d)", (long long)M, D);
+  EVP_CHECK_ARG(ln_shape_ok(M, D), EVP_ESHAPE, "evp_layernorm_fwd: need M>0, D%%4==0, D<=4096 (M=%lld D=%d)", (long long)M, D);
   hipStream_t s = (hipStream_t)stream;
   DISPATCH_VPL(D, hipLaunchKernelGGL(ln_fwd_kernel<V>, dim3(ln_grid(M, LN_FWD_BLOCKS)), dim3(LN_THREADS), 0, s, x, x2, x3, gamma, beta, M, D, eps, y, y_dtype, mean, rstd));
   EVP_CHECK_LAUNCH("evp_layernorm_fwd");
@@ -773,20 +682,12 @@ extern "C" int evp_layernorm_bwd(const void *dy, int dy_dtype, const float *x, c
                                  float *dx, void *dx_lp, float *dgamma, float *dbeta, float *workspace, void *stream) {
   EVP_CHECK_ARG(dy && x && gamma && mean && rstd && workspace, EVP_EINVAL, "evp_layernorm_bwd: null pointer");
   EVP_CHECK_ARG(dx || dx_lp, EVP_EINVAL, "evp_layernorm_bwd: no output requested");
-  EVP_CHECK_ARG(M > 0 && D > 0 && D % 4 == 0 && D <= 4096, EVP_ESHAPE, "evp_layernorm_bwd: need D%%4==0, D<=4096 (D=%d)", D);
-  hipStream_t s = (hipStream_t)stream;
-  const int g = ln_grid(M);
+  EVP_CHECK_ARG(ln_shape_ok(M, D), EVP_ESHAPE, "evp_layernorm_bwd: need D%%4==0, D<=4096 (D=%d)", D);
   const size_t sh = (size_t)ROWS_PER_BLOCK * 2 * D * sizeof(float);
-  DISPATCH_VPL(D, {
-    if (sh > 48 * 1024) (void)hipFuncSetAttribute(reinterpret_cast<const void *>(ln_bwd_kernel<V, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh);
-    hipLaunchKernelGGL((ln_bwd_kernel<V, false>), dim3(g), dim3(LN_THREADS), sh, s, dy, dy_dtype, x, x2, x3, gamma, mean, rstd, gres, M, D, dx, dx_lp, workspace);
-  });
-  EVP_CHECK_LAUNCH("evp_layernorm_bwd");
-  if (dgamma || dbeta) {   // both NULL: the caller reduces the per-block partials workspace[g][2][D] itself (deferred, grouped)
-    hipLaunchKernelGGL(ln_bwd_finalize, dim3((2 * D + 63) / 64), dim3(1024), 0, s, workspace, g, D, dgamma, dbeta);
-    EVP_CHECK_LAUNCH("evp_layernorm_bwd(finalize)");
-  }
-  return EVP_OK;
+  int rc;
+  DISPATCH_VPL(D, rc = ln_bwd_launch("evp_layernorm_bwd", ln_bwd_kernel<V, false>, ln_grid(M), sh, (hipStream_t)stream, workspace, D, dgamma, dbeta,
+                                     dy, dy_dtype, x, x2, x3, gamma, mean, rstd, gres, M, D, dx, dx_lp, workspace));
+  return rc;
 }
 
 extern "C" int evp_layernorm_bwd_cs(const void *dy, int dy_dtype, const float *x, const float *x2, const float *x3,
@@ -794,22 +695,15 @@ extern "C" int evp_layernorm_bwd_cs(const void *dy, int dy_dtype, const float *x
                                     float *dx, void *dx_lp, float *workspace, void *stream) {
   EVP_CHECK_ARG(dy && x && gamma && mean && rstd && workspace, EVP_EINVAL, "evp_layernorm_bwd_cs: null pointer");
   EVP_CHECK_ARG(dx || dx_lp, EVP_EINVAL, "evp_layernorm_bwd_cs: no output requested");
-  EVP_CHECK_ARG(M > 0 && D > 0 && D % 4 == 0 && D <= 4096, EVP_ESHAPE, "evp_layernorm_bwd_cs: need D%%4==0, D<=4096 (D=%d)", D);
-  hipStream_t s = (hipStream_t)stream;
-  const int g = ln_grid(M);
+  EVP_CHECK_ARG(ln_shape_ok(M, D), EVP_ESHAPE, "evp_layernorm_bwd_cs: need D%%4==0, D<=4096 (D=%d)", D);
   const size_t sh = (size_t)ROWS_PER_BLOCK * 3 * D * sizeof(float);
   // three partial rows per wave live in LDS: 160 KiB per workgroup is the limit (D <= 3412 at 4 rows per block); wider rows take
   // evp_layernorm_bwd (two partial rows) plus a column sum of dx (ops.layernorm_bwd does that by itself)
   EVP_CHECK_ARG(sh <= 160 * 1024, EVP_ESHAPE, "evp_layernorm_bwd_cs: D=%d needs %zu bytes of LDS (> 160 KiB); use evp_layernorm_bwd", D, sh);
-  DISPATCH_VPL(D, {
-    if (sh > 48 * 1024) {
-      hipError_t ea = hipFuncSetAttribute(reinterpret_cast<const void *>(ln_bwd_kernel<V, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh);
-      EVP_CHECK_ARG(ea == hipSuccess, EVP_ELAUNCH, "evp_layernorm_bwd_cs: hipFuncSetAttribute(%zu) failed: %s", sh, hipGetErrorString(ea));
-    }
-    hipLaunchKernelGGL((ln_bwd_kernel<V, true>), dim3(g), dim3(LN_THREADS), sh, s, dy, dy_dtype, x, x2, x3, gamma, mean, rstd, gres, M, D, dx, dx_lp, workspace);
-  });
-  EVP_CHECK_LAUNCH("evp_layernorm_bwd_cs");
-  return EVP_OK;
+  int rc;
+  DISPATCH_VPL(D, rc = ln_bwd_launch("evp_layernorm_bwd_cs", ln_bwd_kernel<V, true>, ln_grid(M), sh, (hipStream_t)stream, workspace, D, nullptr, nullptr,
+                                     dy, dy_dtype, x, x2, x3, gamma, mean, rstd, gres, M, D, dx, dx_lp, workspace));
+  return rc;
 }
 
 extern "C" int evp_colsum_nblk(int64_t M) { return (int)((M + CS_ROWS - 1) / CS_ROWS); }
@@ -840,7 +734,7 @@ extern "C" int evp_embed_post_fwd(const float *y, const float *gamma, const floa
                                   const int64_t *ids_keep, int B, int n_keep, int L, int D, float eps, float *out, float *mean,
                                   float *rstd, void *stream) {
   EVP_CHECK_ARG(y && gamma && beta && out && mean && rstd, EVP_EINVAL, "evp_embed_post_fwd: null pointer");
-  EVP_CHECK_ARG(B > 0 && n_keep > 0 && n_keep <= L && D > 0 && D % 4 == 0 && D <= 4096, EVP_ESHAPE, "evp_embed_post_fwd: bad shape");
+  EVP_CHECK_ARG(B > 0 && n_keep > 0 && n_keep <= L && ln_shape_ok((int64_t)B * n_keep, D), EVP_ESHAPE, "evp_embed_post_fwd: bad shape");
   hipStream_t s = (hipStream_t)stream;
   const int64_t M = (int64_t)B * n_keep;
   DISPATCH_VPL(D, hipLaunchKernelGGL(embed_post_fwd_kernel<V>, dim3(ln_grid(M)), dim3(LN_THREADS), 0, s, y, gamma, beta, pos, ids_keep, M, n_keep, L, D, eps, out, mean, rstd));
@@ -852,23 +746,45 @@ extern "C" int evp_embed_post_bwd(const float *g, const float *y, const float *g
                                   const float *rstd, int64_t M, int D, void *dy, int dy_dtype, float *dgamma, float *dbeta,
                                   float *workspace, void *stream) {
   EVP_CHECK_ARG(g && y && gamma && beta && mean && rstd && dy && workspace, EVP_EINVAL, "evp_embed_post_bwd: null pointer");
-  EVP_CHECK_ARG(M > 0 && D > 0 && D % 4 == 0 && D <= 4096, EVP_ESHAPE, "evp_embed_post_bwd: bad shape");
-  hipStream_t s = (hipStream_t)stream;
-  const int gsz = ln_grid(M);
+  EVP_CHECK_ARG(ln_shape_ok(M, D), EVP_ESHAPE, "evp_embed_post_bwd: bad shape");
   const size_t sh = (size_t)ROWS_PER_BLOCK * 2 * D * sizeof(float);
-  DISPATCH_VPL(D, {
-    if (sh > 48 * 1024) (void)hipFuncSetAttribute(reinterpret_cast<const void *>(embed_post_bwd_kernel<V>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh);
-    hipLaunchKernelGGL(embed_post_bwd_kernel<V>, dim3(gsz), dim3(LN_THREADS), sh, s, g, y, gamma, beta, mean, rstd, M, D, dy, dy_dtype, workspace);
-  });
-  EVP_CHECK_LAUNCH("evp_embed_post_bwd");
-  if (dgamma || dbeta) {   // both NULL: the caller reduces the per-block partials workspace[g][2][D] itself (deferred, grouped)
-    hipLaunchKernelGGL(ln_bwd_finalize, dim3((2 * D + 63) / 64), dim3(1024), 0, s, workspace, gsz, D, dgamma, dbeta);
-    EVP_CHECK_LAUNCH("evp_embed_post_bwd(finalize)");
-  }
-  return EVP_OK;
+  int rc;
+  DISPATCH_VPL(D, rc = ln_bwd_launch("evp_embed_post_bwd", embed_post_bwd_kernel<V>, ln_grid(M), sh, (hipStream_t)stream, workspace, D, dgamma, dbeta,
+                                     g, y, gamma, beta, mean, rstd, M, D, dy, dy_dtype, workspace));
+  return rc;
 }
 
 extern "C" int evp_batchnorm_nblk(int64_t R) { return (int)((R + BN_ROWS - 1) / BN_ROWS); }
+
+// the three launches of a BatchNorm direction at one width; grids: (256-column block, slab), 64 columns, 256 x W elements (capped)
+static inline int bn_apply_grid(int64_t total, int W) {
+  const int64_t g = (total / W + 255) / 256;
+  return (int)(g > 4096 ? 4096 : g);
+}
+template <int W>
+static int bn_fwd_launch(const void *x, int dtype, int64_t R, int C, const float *gamma, const float *beta, float eps, float momentum, int relu,
+                         void *y, float *mean, float *invstd, float *running_mean, float *running_var, float *workspace, hipStream_t s) {
+  const int ns = evp_batchnorm_nblk(R);
+  hipLaunchKernelGGL(bn_stats_partial<W>, dim3((C + 255) / 256, ns), dim3(256), 0, s, x, dtype, R, C, workspace);
+  EVP_CHECK_LAUNCH("evp_batchnorm_fwd(stats)");
+  hipLaunchKernelGGL(bn_stats_finalize, dim3((C + 63) / 64), dim3(1024), 0, s, workspace, ns, R, C, eps, momentum, mean, invstd, running_mean, running_var);
+  EVP_CHECK_LAUNCH("evp_batchnorm_fwd(finalize)");
+  hipLaunchKernelGGL(bn_apply<W>, dim3(bn_apply_grid(R * C, W)), dim3(256), 0, s, x, dtype, R * C, C, gamma, beta, mean, invstd, relu, y);
+  EVP_CHECK_LAUNCH("evp_batchnorm_fwd(apply)");
+  return EVP_OK;
+}
+template <int W>
+static int bn_bwd_launch(const void *dy, const void *x, const void *y, int dtype, int64_t R, int C, const float *gamma, const float *mean,
+                         const float *invstd, int relu, void *dx, float *sum_dy, float *sum_dy_xhat, float *workspace, hipStream_t s) {
+  const int ns = evp_batchnorm_nblk(R);
+  hipLaunchKernelGGL(bn_bwd_partial<W>, dim3((C + 255) / 256, ns), dim3(256), 0, s, dy, x, y, dtype, R, C, mean, invstd, relu, workspace);
+  EVP_CHECK_LAUNCH("evp_batchnorm_bwd(partial)");
+  hipLaunchKernelGGL(bn_bwd_finalize, dim3((C + 63) / 64), dim3(1024), 0, s, workspace, ns, C, sum_dy, sum_dy_xhat);
+  EVP_CHECK_LAUNCH("evp_batchnorm_bwd(finalize)");
+  hipLaunchKernelGGL(bn_bwd_apply<W>, dim3(bn_apply_grid(R * C, W)), dim3(256), 0, s, dy, x, y, dtype, R, C, gamma, mean, invstd, relu, sum_dy, sum_dy_xhat, dx);
+  EVP_CHECK_LAUNCH("evp_batchnorm_bwd(apply)");
+  return EVP_OK;
+}
 
 extern "C" int evp_batchnorm_fwd(const void *x, int dtype, int64_t R, int C, const float *gamma, const float *beta, float eps,
                                  float momentum, int relu, void *y, float *mean, float *invstd, float *running_mean,
@@ -876,20 +792,9 @@ extern "C" int evp_batchnorm_fwd(const void *x, int dtype, int64_t R, int C, con
   EVP_CHECK_ARG(x && y && mean && invstd && workspace, EVP_EINVAL, "evp_batchnorm_fwd: null pointer");
   EVP_CHECK_ARG(R > 1 && C > 0, EVP_ESHAPE, "evp_batchnorm_fwd: need R>1 rows");
   EVP_CHECK_ARG((gamma == nullptr) == (beta == nullptr), EVP_EINVAL, "evp_batchnorm_fwd: gamma and beta go together");
-  hipStream_t s = (hipStream_t)stream;
-  const int ns = evp_batchnorm_nblk(R);
   const bool v4 = (C % 4 == 0) && (((uintptr_t)x | (uintptr_t)y) & 15) == 0;
-  if (v4) hipLaunchKernelGGL(bn_stats_partial_v4, dim3((C + 255) / 256, ns), dim3(256), 0, s, x, dtype, R, C, workspace);
-  else hipLaunchKernelGGL(bn_stats_partial, dim3((C + 255) / 256, ns), dim3(256), 0, s, x, dtype, R, C, workspace);
-  EVP_CHECK_LAUNCH("evp_batchnorm_fwd(stats)");
-  hipLaunchKernelGGL(bn_stats_finalize, dim3((C + 63) / 64), dim3(1024), 0, s, workspace, ns, R, C, eps, momentum, mean, invstd, running_mean, running_var);
-  EVP_CHECK_LAUNCH("evp_batchnorm_fwd(finalize)");
-  const int64_t total = R * C;
-  int64_t g = ((v4 ? total / 4 : total) + 255) / 256; if (g > 4096) g = 4096;
-  if (v4) hipLaunchKernelGGL(bn_apply_v4, dim3((int)g), dim3(256), 0, s, x, dtype, total / 4, C, gamma, beta, mean, invstd, relu, y);
-  else hipLaunchKernelGGL(bn_apply, dim3((int)g), dim3(256), 0, s, x, dtype, total, C, gamma, beta, mean, invstd, relu, y);
-  EVP_CHECK_LAUNCH("evp_batchnorm_fwd(apply)");
-  return EVP_OK;
+  return (v4 ? bn_fwd_launch<4> : bn_fwd_launch<1>)(x, dtype, R, C, gamma, beta, eps, momentum, relu, y, mean, invstd, running_mean, running_var,
+                                                    workspace, (hipStream_t)stream);
 }
 
 extern "C" int evp_batchnorm_bwd(const void *dy, const void *x, const void *y, int dtype, int64_t R, int C, const float *gamma,
@@ -898,19 +803,10 @@ extern "C" int evp_batchnorm_bwd(const void *dy, const void *x, const void *y, i
   EVP_CHECK_ARG(dy && x && mean && invstd && dx && workspace, EVP_EINVAL, "evp_batchnorm_bwd: null pointer");
   EVP_CHECK_ARG(!relu || y, EVP_EINVAL, "evp_batchnorm_bwd: relu needs y");
   hipStream_t s = (hipStream_t)stream;
-  const int ns = evp_batchnorm_nblk(R);
-  float *sum_dy = workspace + (int64_t)ns * 2 * C, *sum_dy_xhat = sum_dy + C;
+  float *sum_dy = workspace + (int64_t)evp_batchnorm_nblk(R) * 2 * C, *sum_dy_xhat = sum_dy + C;
   const bool v4 = (C % 4 == 0) && (((uintptr_t)dy | (uintptr_t)x | (uintptr_t)y | (uintptr_t)dx) & 15) == 0;
-  if (v4) hipLaunchKernelGGL(bn_bwd_partial_v4, dim3((C + 255) / 256, ns), dim3(256), 0, s, dy, x, y, dtype, R, C, mean, invstd, relu, workspace);
-  else hipLaunchKernelGGL(bn_bwd_partial, dim3((C + 255) / 256, ns), dim3(256), 0, s, dy, x, y, dtype, R, C, mean, invstd, relu, workspace);
-  EVP_CHECK_LAUNCH("evp_batchnorm_bwd(partial)");
-  hipLaunchKernelGGL(bn_bwd_finalize, dim3((C + 63) / 64), dim3(1024), 0, s, workspace, ns, C, sum_dy, sum_dy_xhat);
-  EVP_CHECK_LAUNCH("evp_batchnorm_bwd(finalize)");
-  const int64_t total = R * C;
-  int64_t g = ((v4 ? total / 4 : total) + 255) / 256; if (g > 4096) g = 4096;
-  if (v4) hipLaunchKernelGGL(bn_bwd_apply_v4, dim3((int)g), dim3(256), 0, s, dy, x, y, dtype, total / 4, R, C, gamma, mean, invstd, relu, sum_dy, sum_dy_xhat, dx);
-  else hipLaunchKernelGGL(bn_bwd_apply, dim3((int)g), dim3(256), 0, s, dy, x, y, dtype, R, C, gamma, mean, invstd, relu, sum_dy, sum_dy_xhat, dx);
-  EVP_CHECK_LAUNCH("evp_batchnorm_bwd(apply)");
+  const int rc = (v4 ? bn_bwd_launch<4> : bn_bwd_launch<1>)(dy, x, y, dtype, R, C, gamma, mean, invstd, relu, dx, sum_dy, sum_dy_xhat, workspace, s);
+  if (rc != EVP_OK) return rc;
   hipError_t e = hipSuccess;
   if (dgamma) e = hipMemcpyAsync(dgamma, sum_dy_xhat, sizeof(float) * C, hipMemcpyDeviceToDevice, s);
   if (dbeta && e == hipSuccess) e = hipMemcpyAsync(dbeta, sum_dy, sizeof(float) * C, hipMemcpyDeviceToDevice, s);

@@ -56,12 +56,7 @@ __global__ __launch_bounds__(256) void adamw_kernel(const AdamArgs a) {
     reinterpret_cast<float4 *>(p)[i] = pp;
     reinterpret_cast<float4 *>(m)[i] = mm;
     reinterpret_cast<float4 *>(v)[i] = vv;
-    if (lp) {
-      uint2 u;
-      u.x = (uint32_t)f32_to_bf16(pp.x) | ((uint32_t)f32_to_bf16(pp.y) << 16);
-      u.y = (uint32_t)f32_to_bf16(pp.z) | ((uint32_t)f32_to_bf16(pp.w) << 16);
-      reinterpret_cast<uint2 *>(lp)[i] = u;
-    }
+    if (lp) reinterpret_cast<uint2 *>(lp)[i] = pack4_bf16(pp);
   }
   for (int64_t i = c4 * 4 + threadIdx.x; i < cnt; i += 256) {
     const float gr = g[i] * grad_scale;

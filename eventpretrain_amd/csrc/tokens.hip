@@ -89,12 +89,7 @@ __global__ __launch_bounds__(256) void patchify_kernel(const float *x, const int
     const int c = e / (p * p), rem = e % (p * p), py = rem / p, px = rem % p;
     const float4 v = *reinterpret_cast<const float4 *>(xb + ((int64_t)c * H + gy * p + py) * W + gx * p + px);
     if constexpr (sizeof(T) == 4) *reinterpret_cast<float4 *>(o + e) = v;
-    else {
-      uint2 u;
-      u.x = (uint32_t)f32_to_bf16(v.x) | ((uint32_t)f32_to_bf16(v.y) << 16);
-      u.y = (uint32_t)f32_to_bf16(v.z) | ((uint32_t)f32_to_bf16(v.w) << 16);
-      *reinterpret_cast<uint2 *>(o + e) = u;
-    }
+    else *reinterpret_cast<uint2 *>(o + e) = pack4_bf16(v);
   }
 }
 
@@ -196,20 +191,7 @@ __global__ __launch_bounds__(256) void cast_kernel(const void *src, int sd, void
   // 4 elements per thread where alignment allows (buffers from torch are >= 256-byte aligned)
   const int64_t n4 = n >> 2;
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (int64_t)gridDim.x * 256) {
-    float4 v;
-    if (sd == EVP_F32) v = reinterpret_cast<const float4 *>(src)[i];
-    else {
-      const uint2 u = reinterpret_cast<const uint2 *>(src)[i];
-      v = make_float4(__uint_as_float(u.x << 16), __uint_as_float(u.x & 0xFFFF0000u), __uint_as_float(u.y << 16),
-                      __uint_as_float(u.y & 0xFFFF0000u));
-    }
-    if (dd == EVP_F32) reinterpret_cast<float4 *>(dst)[i] = v;
-    else {
-      uint2 u;
-      u.x = (uint32_t)f32_to_bf16(v.x) | ((uint32_t)f32_to_bf16(v.y) << 16);
-      u.y = (uint32_t)f32_to_bf16(v.z) | ((uint32_t)f32_to_bf16(v.w) << 16);
-      reinterpret_cast<uint2 *>(dst)[i] = u;
-    }
+    st4_any(dst, dd, i * 4, ld4_any(src, sd, i * 4));
   }
   if (blockIdx.x == 0 && threadIdx.x < (n & 3)) {
     const int64_t i = (n & ~(int64_t)3) + threadIdx.x;
