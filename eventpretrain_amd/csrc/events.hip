@@ -25,7 +25,7 @@ __device__ __forceinline__ bool key_less(const SortKey &a, const SortKey &b) { r
 // one workgroup per clip: gather + perturb + clip the added rows, bitonic-sort them by (t, draw order) in LDS
 __global__ __launch_bounds__(1024) void build_added_kernel(const double *events, const int64_t *clip_begin, const int64_t *add_idx,
                                                            const double *add_noise, const int64_t *add_offsets, double sensor_w,
-                                                           double sensor_h, double *add_rows) {
+                                                           double sensor_h, const int32_t *clip_hw, double *add_rows) {
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
   SortKey *keys = reinterpret_cast<SortKey *>(smem_raw);
   const int c = blockIdx.x;
@@ -33,6 +33,10 @@ __global__ __launch_bounds__(1024) void build_added_kernel(const double *events,
   const int na = (int)(add_offsets[c + 1] - a0);
   if (na <= 0) return;
   const double *ev = events + clip_begin[c] * 4;
+  if (clip_hw) {                          // the clip's own grid (H_c, W_c) in place of the sensor's (ft_n_cars_dataset.py:64-70)
+    sensor_h = (double)clip_hw[c * 2];
+    sensor_w = (double)clip_hw[c * 2 + 1];
+  }
   int np2 = 1;
   while (np2 < na) np2 <<= 1;
   for (int j = threadIdx.x; j < np2; j += blockDim.x) {
@@ -340,6 +344,29 @@ __global__ __launch_bounds__(1024) void draw_erase_add_kernel(const int64_t *win
 // needs nothing from the host per batch: `state` = (step, first sample) lives on the device and is advanced here.
 struct CropGeom { double area, a0, da; int W, H; };      // a0 = W / H * 3/4, da = W / H * 4/3 - a0 (computed by the caller in double)
 
+// as the numpy form: W / H * ratio[0] + u * (W / H * ratio[1] - W / H * ratio[0]) -- on the host for a grid every clip shares, on the
+// device for a clip's own grid
+__host__ __device__ inline CropGeom crop_geom(int H, int W) {
+#pragma clang fp contract(off)
+  CropGeom g;
+  g.W = W; g.H = H;
+  g.area = (double)((int64_t)W * H);
+  const double wh = (double)W / (double)H;
+  g.a0 = wh * (3.0 / 4.0);
+  g.da = wh * (4.0 / 3.0) - wh * (3.0 / 4.0);
+  return g;
+}
+
+// the 52 uniforms of purpose 4 behind one sample's crop box and flip coins (view_augment.py evg_uniforms)
+__device__ __forceinline__ void crop_uniform_block(uint64_t seed, uint64_t step, uint64_t sample, int b, double *U) {      // U[4 b .. 4 b + 4)
+  uint32_t q[4] = {(uint32_t)b, 4u, (uint32_t)sample, (uint32_t)(sample >> 32)};
+  ev_philox(q, (uint32_t)seed ^ (uint32_t)(step * 0x9E3779B97F4A7C15ull >> 32), (uint32_t)(seed >> 32) ^ (uint32_t)step);
+  for (int i = 0; i < 4; ++i) U[b * 4 + i] = (double)q[i] * 2.3283064365386963e-10;
+}
+__device__ __forceinline__ void crop_uniforms(uint64_t seed, uint64_t step, uint64_t sample, double *U) {
+  for (int b = 0; b < 13; ++b) crop_uniform_block(seed, step, sample, b, U);
+}
+
 __device__ void plan_crop_row(const double *U, const CropGeom g, double crop_min, double one_minus, int32_t *row) {
 #pragma clang fp contract(off)
   long cw1 = g.W, ch1 = g.H;
@@ -391,11 +418,7 @@ __global__ __launch_bounds__(256) void plan_batch_kernel(const int64_t *clip_off
     tabs[(nc + 1) + c] = clip_off[c] + s1;
     plan_sm[c] = e; plan_sm[nc + c] = a; plan_sm[2 * nc + c] = nw - e + a;
     double U[52];
-    for (int b = 0; b < 13; ++b) {
-      uint32_t q[4] = {(uint32_t)b, 4u, (uint32_t)sample, (uint32_t)(sample >> 32)};
-      ev_philox(q, (uint32_t)seed ^ (uint32_t)(step * 0x9E3779B97F4A7C15ull >> 32), (uint32_t)(seed >> 32) ^ (uint32_t)step);
-      for (int i = 0; i < 4; ++i) U[b * 4 + i] = (double)q[i] * 2.3283064365386963e-10;
-    }
+    crop_uniforms(seed, step, sample, U);
     plan_crop_row(U, grid, crop_min, one_minus, params + c * 6);
     if (fparams) {
       plan_crop_row(U, frame, crop_min, one_minus, fparams + c * 6);
@@ -418,11 +441,72 @@ __global__ __launch_bounds__(256) void plan_batch_kernel(const int64_t *clip_off
     if (advance) state[0] = (int64_t)(step + 1);
   }
 }
+
+// ---- per-clip WINDOW GEOMETRY (N-Cars, ft_n_cars_dataset.py:61-87): the grid of a sample is H_c = int(max y) + 1 by W_c = int(max x) + 1
+// over the rows of its picked window, taken before the event augmentation; it bounds the added rows, sizes the voxel grid and is the view
+// view_crop draws its box on. One workgroup per clip: lanes stride over the window, (x, y) of a row as one 16-byte load; max and min go
+// wave shuffle -> LDS -> thread 0, which writes (H_c, W_c) and the clip's crop row -- plan_crop_row on the clip's own CropGeom, from the
+// uniforms plan_batch_kernel draws for the sample (thirteen lanes draw a Philox block each meanwhile) -- or, without draw_crop, the full box (view_resize alone). K1 and the view kernels run
+// unchanged on a grid of the CAPACITY (cap_h, cap_w): the clip's cells are the top-left H_c x W_c of it, the rest stays zero.
+// A window that is empty, holds a negative coordinate or reaches past the capacity is refused: its extent is clamped into [1, cap] (so
+// every row written is a valid box of the capacity grid) and the status word counts it.
+constexpr int GEOM_THREADS = 1024;     // a 3000-row window is three loads per lane: the kernel is bound by their latency, not by bytes
+__global__ __launch_bounds__(GEOM_THREADS) void window_geometry_kernel(const double *events, const int64_t *win_begin, const int64_t *win_end, int cap_h,
+                                                                      int cap_w, int draw_crop, double crop_min, double one_minus, uint64_t seed,
+                                                                      uint64_t step, int64_t first_sample, const int64_t *step_first, int32_t *clip_hw,
+                                                                      int32_t *params, int32_t *status) {
+  __shared__ double s_red[4][GEOM_THREADS / 64];
+  __shared__ double s_U[52];
+  const int c = blockIdx.x;
+  if (draw_crop && threadIdx.x >= GEOM_THREADS - 13) {      // the clip's uniforms, one Philox block per lane of the last wave, under the loads
+    if (step_first) {                     // (step, first sample) of THIS batch, as the plan kernel of a captured chain left them
+      step = (uint64_t)step_first[0];
+      first_sample = step_first[1];
+    }
+    crop_uniform_block(seed, step, (uint64_t)(first_sample + c), GEOM_THREADS - 1 - (int)threadIdx.x, s_U);
+  }
+  const int64_t beg = win_begin[c], n = win_end[c] - beg;
+  const double inf = __builtin_inf();
+  double xmax = -inf, ymax = -inf, xmin = inf, ymin = inf;
+  const double *ev = events + beg * 4;
+  for (int64_t i = threadIdx.x; i < n; i += GEOM_THREADS) {
+    const double2 xy = *reinterpret_cast<const double2 *>(ev + i * 4);
+    xmax = fmax(xmax, xy.x); xmin = fmin(xmin, xy.x);
+    ymax = fmax(ymax, xy.y); ymin = fmin(ymin, xy.y);
+  }
+  for (int off = 32; off > 0; off >>= 1) {
+    xmax = fmax(xmax, __shfl_down(xmax, off, 64)); xmin = fmin(xmin, __shfl_down(xmin, off, 64));
+    ymax = fmax(ymax, __shfl_down(ymax, off, 64)); ymin = fmin(ymin, __shfl_down(ymin, off, 64));
+  }
+  if ((threadIdx.x & 63) == 0) {
+    const int w = threadIdx.x >> 6;
+    s_red[0][w] = xmax; s_red[1][w] = ymax; s_red[2][w] = xmin; s_red[3][w] = ymin;
+  }
+  __syncthreads();
+  if (threadIdx.x != 0) return;
+  for (int w = 1; w < GEOM_THREADS / 64; ++w) {
+    xmax = fmax(xmax, s_red[0][w]); ymax = fmax(ymax, s_red[1][w]);
+    xmin = fmin(xmin, s_red[2][w]); ymin = fmin(ymin, s_red[3][w]);
+  }
+  // int(max) + 1 <= cap  <=>  max < cap; the comparisons are written so that a NaN or an empty window (max = -inf) is refused as well
+  const bool ok = n > 0 && xmin >= 0.0 && ymin >= 0.0 && xmax < (double)cap_w && ymax < (double)cap_h;
+  if (!ok) atomicAdd(status, 1);
+  const int H = ok ? (int)ymax + 1 : (ymax >= (double)cap_h ? cap_h : (ymax >= 0.0 ? (int)ymax + 1 : 1));
+  const int W = ok ? (int)xmax + 1 : (xmax >= (double)cap_w ? cap_w : (xmax >= 0.0 ? (int)xmax + 1 : 1));
+  clip_hw[c * 2] = H;
+  clip_hw[c * 2 + 1] = W;
+  int32_t *row = params + c * 6;
+  if (draw_crop) {
+    plan_crop_row(s_U, crop_geom(H, W), crop_min, one_minus, row);
+  } else {
+    row[0] = 0; row[1] = 0; row[2] = W; row[3] = H; row[4] = 0; row[5] = 0;
+  }
+}
 }  // namespace
 
 static int build_added_launch(const double *events, const int64_t *clip_begin, int n_clips, const int64_t *add_idx, const double *add_noise,
-                              const int64_t *add_offsets, int max_add_per_clip, double sensor_w, double sensor_h, double *add_rows_ws, hipStream_t s,
-                              const char *who) {
+                              const int64_t *add_offsets, int max_add_per_clip, double sensor_w, double sensor_h, const int32_t *clip_hw,
+                              double *add_rows_ws, hipStream_t s, const char *who) {
   int np2 = 1;
   while (np2 < max_add_per_clip) np2 <<= 1;
   const size_t smem = (size_t)np2 * sizeof(SortKey);
@@ -431,7 +515,7 @@ static int build_added_launch(const double *events, const int64_t *clip_begin, i
     EVP_CHECK_ARG(e == hipSuccess, EVP_ELAUNCH, "%s: cannot reserve %zu B of LDS: %s", who, smem, hipGetErrorString(e));
   }
   hipLaunchKernelGGL(build_added_kernel, dim3(n_clips), dim3(1024), smem, s, events, clip_begin, add_idx, add_noise, add_offsets, sensor_w, sensor_h,
-                     add_rows_ws);
+                     clip_hw, add_rows_ws);
   EVP_CHECK_LAUNCH(who);
   return EVP_OK;
 }
@@ -449,7 +533,7 @@ static int erase_add_launch(const double *events, const int64_t *clip_begin, con
   EVP_CHECK_ARG((((uintptr_t)events | (uintptr_t)out_events) & 15) == 0, EVP_EINVAL, "%s: event buffers must be 16-byte aligned", who);
   hipStream_t s = (hipStream_t)stream;
   if (max_add_per_clip > 0) {
-    int rc = build_added_launch(events, clip_begin, n_clips, add_idx, add_noise, add_offsets, max_add_per_clip, sensor_w, sensor_h, add_rows_ws, s, who);
+    int rc = build_added_launch(events, clip_begin, n_clips, add_idx, add_noise, add_offsets, max_add_per_clip, sensor_w, sensor_h, nullptr, add_rows_ws, s, who);
     if (rc) return rc;
   }
   hipLaunchKernelGGL(merge_kernel, dim3(64, n_clips), dim3(256), 0, s, events, clip_begin, clip_end, erase_idx, erase_offsets, add_offsets, add_rows_ws,
@@ -475,14 +559,21 @@ extern "C" int evp_events_erase_add_win_f64(const double *events, const int64_t 
                           sensor_h, add_rows_ws, out_offsets, out_events, stream, "evp_events_erase_add_win_f64");
 }
 
+extern "C" int evp_events_build_added_hw_f64(const double *events, const int64_t *win_begin, int n_clips, const int64_t *add_idx,
+                                             const double *add_noise, const int64_t *add_offsets, int max_add_per_clip, double sensor_w,
+                                             double sensor_h, const int32_t *clip_hw, double *add_rows, void *stream) {
+  EVP_CHECK_ARG(events && win_begin && add_idx && add_noise && add_offsets && add_rows, EVP_EINVAL, "evp_events_build_added_hw_f64: null pointer");
+  EVP_CHECK_ARG(n_clips > 0 && max_add_per_clip >= 0 && max_add_per_clip <= EA_MAX_ADD, EVP_ESHAPE, "evp_events_build_added_hw_f64: bad shape");
+  if (max_add_per_clip == 0) return EVP_OK;
+  return build_added_launch(events, win_begin, n_clips, add_idx, add_noise, add_offsets, max_add_per_clip, sensor_w, sensor_h, clip_hw, add_rows,
+                            (hipStream_t)stream, "evp_events_build_added_hw_f64");
+}
+
 extern "C" int evp_events_build_added_f64(const double *events, const int64_t *win_begin, int n_clips, const int64_t *add_idx, const double *add_noise,
                                           const int64_t *add_offsets, int max_add_per_clip, double sensor_w, double sensor_h, double *add_rows,
                                           void *stream) {
-  EVP_CHECK_ARG(events && win_begin && add_idx && add_noise && add_offsets && add_rows, EVP_EINVAL, "evp_events_build_added_f64: null pointer");
-  EVP_CHECK_ARG(n_clips > 0 && max_add_per_clip >= 0 && max_add_per_clip <= EA_MAX_ADD, EVP_ESHAPE, "evp_events_build_added_f64: bad shape");
-  if (max_add_per_clip == 0) return EVP_OK;
-  return build_added_launch(events, win_begin, n_clips, add_idx, add_noise, add_offsets, max_add_per_clip, sensor_w, sensor_h, add_rows,
-                            (hipStream_t)stream, "evp_events_build_added_f64");
+  return evp_events_build_added_hw_f64(events, win_begin, n_clips, add_idx, add_noise, add_offsets, max_add_per_clip, sensor_w, sensor_h, nullptr,
+                                       add_rows, stream);
 }
 
 extern "C" int evp_events_draw_erase_add(const int64_t *win_begin, const int64_t *win_end, int n_clips, const int64_t *erase_offsets,
@@ -514,18 +605,23 @@ extern "C" int evp_events_plan_batch(const int64_t *clip_offsets, int n_clips, i
                 "evp_events_plan_batch: bad shape (at most 2048 clips per batch: three int64 rows of the batch live in 48 KiB of LDS)");
   EVP_CHECK_ARG(!frame_params || (frame_h > 0 && frame_w > 0), EVP_ESHAPE, "evp_events_plan_batch: frame size required with frame_params");
   EVP_CHECK_ARG(crop_min > 0.0 && crop_min <= 1.0, EVP_EINVAL, "evp_events_plan_batch: crop_min must lie in (0, 1]");
-  auto geom = [](int H, int W) {
-    CropGeom g;
-    g.W = W; g.H = H;
-    g.area = (double)((int64_t)W * H);
-    const double wh = (double)W / (double)H;          // as the numpy form: W / H * ratio[0] + u * (W / H * ratio[1] - W / H * ratio[0])
-    g.a0 = wh * (3.0 / 4.0);
-    g.da = wh * (4.0 / 3.0) - wh * (3.0 / 4.0);
-    return g;
-  };
-  const CropGeom gg = geom(grid_h, grid_w), gf = frame_params ? geom(frame_h, frame_w) : gg;
+  const CropGeom gg = crop_geom(grid_h, grid_w), gf = frame_params ? crop_geom(frame_h, frame_w) : gg;
   hipLaunchKernelGGL(plan_batch_kernel, dim3(1), dim3(256), (size_t)3 * n_clips * sizeof(int64_t), (hipStream_t)stream, clip_offsets, n_clips,
                      fix_events_num, seed, state, advance, step_first_out, gg, gf, crop_min, 1.0 - crop_min, tabs, params, frame_params);
   EVP_CHECK_LAUNCH("evp_events_plan_batch");
+  return EVP_OK;
+}
+
+extern "C" int evp_events_window_geometry(const double *events, const int64_t *win_begin, const int64_t *win_end, int n_clips, int cap_h, int cap_w,
+                                          int draw_crop, double crop_min, uint64_t seed, uint64_t step, int64_t first_sample,
+                                          const int64_t *step_first_dev, int32_t *clip_hw, int32_t *params, int32_t *status, void *stream) {
+  EVP_CHECK_ARG(events && win_begin && win_end && clip_hw && params && status, EVP_EINVAL, "evp_events_window_geometry: null pointer");
+  EVP_CHECK_ARG(((uintptr_t)events & 15) == 0, EVP_EINVAL, "evp_events_window_geometry: the event buffer must be 16-byte aligned");
+  EVP_CHECK_ARG(n_clips > 0, EVP_ESHAPE, "evp_events_window_geometry: n_clips must be positive");
+  EVP_CHECK_ARG(cap_h > 0 && cap_w > 0, EVP_ESHAPE, "evp_events_window_geometry: the capacity (cap_h, cap_w) must be positive");
+  EVP_CHECK_ARG(crop_min > 0.0 && crop_min <= 1.0, EVP_EINVAL, "evp_events_window_geometry: crop_min must lie in (0, 1]");
+  hipLaunchKernelGGL(window_geometry_kernel, dim3(n_clips), dim3(GEOM_THREADS), 0, (hipStream_t)stream, events, win_begin, win_end, cap_h, cap_w,
+                     draw_crop, crop_min, 1.0 - crop_min, seed, step, first_sample, step_first_dev, clip_hw, params, status);
+  EVP_CHECK_LAUNCH("evp_events_window_geometry");
   return EVP_OK;
 }

@@ -40,18 +40,29 @@ def draw_evg_params_batch(seed, step, B, H, W, crop_min=0.8, first_sample=0, rat
     """int32 [B,6] rows for samples first_sample .. first_sample+B-1 of optimizer step `step`: sample i uses the Philox
     stream keyed by (seed, step, i). Same distribution as the reference's (same accept / reject rule: up to ten tries of
     (area, aspect, swap coin), the first box that fits is placed uniformly, else the whole view; then the two flip coins), vectorised
-    over the batch: every sample draws the uniforms of all ten tries, the first accepted one is used."""
+    over the batch: every sample draws the uniforms of all ten tries, the first accepted one is used.
+    `H`, `W`: the view's size, scalars, or int arrays of length B -- a view of its own per sample (N-Cars: the window's extent; what
+    evp_events_window_geometry draws on the device); row i then equals the scalar call for (H[i], W[i])."""
     if U is None:
         U = evg_uniforms(seed, step, B, first_sample)
     T = U[:, :50].reshape(B, 10, 5)
-    area = W * H
+    if np.ndim(H) or np.ndim(W):
+        H, W = (np.broadcast_to(np.asarray(v, dtype=np.int64), (B,)) for v in (H, W))
+        return _draw_rows(U, T, H, W, H[:, None], W[:, None], crop_min, ratio)
+    return _draw_rows(U, T, H, W, H, W, crop_min, ratio)
+
+
+def _draw_rows(U, T, H, W, Ht, Wt, crop_min, ratio):
+    """draw_evg_params_batch's arithmetic: (H, W) as they meet the per-sample columns, (Ht, Wt) as they meet the [B, 10] tries."""
+    B = U.shape[0]
+    area = Wt * Ht
     target = (crop_min + T[..., 0] * (1.0 - crop_min)) * area
-    aspect = W / H * ratio[0] + T[..., 1] * (W / H * ratio[1] - W / H * ratio[0])
+    aspect = Wt / Ht * ratio[0] + T[..., 1] * (Wt / Ht * ratio[1] - Wt / Ht * ratio[0])
     cw = np.rint(np.sqrt(target * aspect)).astype(np.int64)
     ch = np.rint(np.sqrt(target / aspect)).astype(np.int64)
     swap = (T[..., 2] * 10).astype(np.int64) < 5
     cw, ch = np.where(swap, ch, cw), np.where(swap, cw, ch)
-    ok = (cw < W) & (ch < H)
+    ok = (cw < Wt) & (ch < Ht)
     first = np.argmax(ok, axis=1)
     any_ok = ok.any(axis=1)
     r = np.arange(B)

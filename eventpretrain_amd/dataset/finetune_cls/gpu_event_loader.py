@@ -15,6 +15,17 @@ Two recipes, chosen by the caller (`grid`, `sensor`; `finetune_recipe(args)` map
                  ft_dvs128_gesture_dataset.py:63-89 and siblings): no events_reshape, voxelise at the sensor's (H, W), crop boxes on the
                  H x W grid, evg_augment (train) / view_resize (val) resizes H x W -> S x S in args.resize_mode.
 
+  grid="window"  N-Cars (ft_n_cars_dataset.py:61-87; `ncars_recipe(args)`): as grid="sensor", but every sample's grid is its own window's
+                 extent, H_c = int(max y) + 1 by W_c = int(max x) + 1, taken before the event augmentation -- the bound of the added rows,
+                 the voxel grid's size and the view view_crop draws its box on. `sensor` is the CAPACITY (cap_h, cap_w): K1 and the view
+                 kernels run on padded cap_h x cap_w grids of which a clip fills the top-left H_c x W_c, the per-clip geometry travels in
+                 the crop rows (evp_events_window_geometry writes them; evp_events_build_added_hw_f64 clips the added rows per clip).
+                 Bit for bit the reference's chain (tests/golden/ft_ncars_recipe.npz) except a 1 x 1 window grid in bilinear mode, where
+                 ATen takes another path and differs by 1 ulp. Every window is checked on the host before upload (non-empty, coordinates
+                 >= 0 and inside the capacity: ValueError naming the clip); the device's own count of refused windows is read once at the
+                 end of a pass. Clean validation: the geometry kernel on the uploaded windows, K1 algo 3 at the capacity, the view kernel
+                 under the clips' full boxes.
+
 Train: one replay of the self-driven captured chain (gpu_input_pipeline.CapturedChain) with `resize_mode=args.resize_mode` -- the
 reference's fine-tuning default is 'bilinear' (main_finetune_cls.py:48) -- and windows of args.fix_events_num rows.
 Val: the window pick with args.val_fix_events_num (get_random_index(is_train=False), events_augment.py:9-20; the same rule on word 0 of
@@ -31,11 +42,12 @@ Labels travel with the windows: packed into the pinned slot, uploaded into a per
 step, which is queued after this loader yields -- so the event the next upload waits for is recorded on the consumer's stream after
 the generator resumes, behind that step, not behind the chain replay.
 
-Out of scope (NotImplementedError): EvRepSL, the 2- and 3-bin representations, N-Cars (per-clip grid sizes; see finetune_recipe). The
+Out of scope (NotImplementedError): EvRepSL, the 2- and 3-bin representations. The
 reference's add_noise_events (events_augment.py) is called by none of its datasets and is not what --val_event_noise means."""
 import numpy as np
 import torch
 
+from ..._lib import call, ptr, stream_ptr
 from ..dataset_utils.events_to_voxel_grid import voxel_grid_batch
 from ..pretrain.gpu_event_loader import ClipWindowLoader
 from ..augmentation.view_augment import evg_augment_batch
@@ -51,12 +63,18 @@ def finetune_recipe(args):
     own argument names for that dataset (cal_sensor_h / _w for N-Caltech101, ...). The loader never calls this on its own."""
     kind = args.dataset_type
     if kind == "n-cars":
-        raise NotImplementedError("finetune_recipe: n-cars sizes each grid from the window's own max(x) + 1 and max(y) + 1; that needs per-clip "
-                                  "forms of the plan kernel's crop geometry and of the added-row clipping")
+        raise NotImplementedError("finetune_recipe: n-cars sizes each grid from the window's own max(x) + 1 and max(y) + 1, so its recipe carries "
+                                  "a capacity in the sensor's place: use ncars_recipe(args)")
     if kind not in _RECIPES:
         raise ValueError(f"finetune_recipe: unknown dataset_type {kind!r} (one of {sorted(_RECIPES)})")
     grid, prefix = _RECIPES[kind]
     return dict(grid=grid, sensor=(int(getattr(args, prefix + "_sensor_h")), int(getattr(args, prefix + "_sensor_w"))))
+
+
+def ncars_recipe(args):
+    """-> dict(grid="window", sensor=(cap_h, cap_w)): GpuFinetuneLoader's recipe keywords for N-Cars, the capacity of the padded grids read
+    from the reference's own cars_sensor_h / cars_sensor_w (100 x 120 where the namespace has none)."""
+    return dict(grid="window", sensor=(int(getattr(args, "cars_sensor_h", 100)), int(getattr(args, "cars_sensor_w", 120))))
 
 
 class GpuFinetuneLoader(ClipWindowLoader):
@@ -78,17 +96,22 @@ class GpuFinetuneLoader(ClipWindowLoader):
                                 view_augment=self.is_train, voxel_cells="f32" if self.is_train else "f64")
         self._setup(args, samples, batch_size, n_batches, seed, first_sample, step0, fix, fix)
         self.S, self.bins, self.resize_mode = int(args.input_size), int(args.num_bins), mode
-        self.sensor, self.grid_hw, self.scale = pipe.sensor, (pipe.gh, pipe.gw), pipe.scale
-        self.pipe = self.chain = self.out = self.raw = None
+        self.sensor, self.grid_hw, self.scale, self.window = pipe.sensor, (pipe.gh, pipe.gw), pipe.scale, pipe.grid == "window"
+        self.pipe = self.chain = self.out = self.raw = self.ext = self.geom_status = None
         if self.is_train or self.noisy_val:
             self.pipe = pipe
             self.chain = pipe.capture(self.ev, self.B, clip_offsets=np.zeros(self.B + 1, np.int64))
             self.d_off = self.chain.d_off
+            self.ext, self.geom_status = self.chain.ext, self.chain.geom_status
         else:
             self.out = torch.zeros(self.B, self.bins, self.S, self.S, dtype=torch.float32, device=self.dev)
-            if self.grid_hw != (self.S, self.S):          # view_resize is a real resize: K1 into the sensor-sized grids, then the view kernel
+            if pipe.resize:                               # view_resize is a real resize: K1 into the sensor-sized grids, then the view kernel
                 self.raw = torch.zeros(self.B, self.bins, *self.grid_hw, dtype=torch.float32, device=self.dev)
-                self._full = pipe.full_rows(self.B, self.dev)
+                # the full-box rows: one constant row, or (window) the clips' own (0, 0, W_c, H_c, 0, 0), written per batch by the geometry kernel
+                self._full = torch.zeros(self.B, 6, dtype=torch.int32, device=self.dev) if self.window else pipe.full_rows(self.B, self.dev)
+            if self.window:
+                self.ext = torch.zeros(self.B, 2, dtype=torch.int32, device=self.dev)
+                self.geom_status = torch.zeros(1, dtype=torch.int32, device=self.dev)
 
     def _alloc_extra(self):
         self._lab = [torch.zeros(self.B, dtype=torch.int64, device=self.dev) for _ in range(2)]
@@ -99,6 +122,29 @@ class GpuFinetuneLoader(ClipWindowLoader):
 
     def _upload_extra(self, slot):
         self._lab[slot].copy_(self._pin_lab[slot], non_blocking=True)
+
+    def _check_window(self, window, name):
+        """grid="window", on the host before upload: what evp_events_window_geometry would refuse (and only count) on the device."""
+        if not self.window:
+            return
+        cap_h, cap_w = self.sensor
+        if window.shape[0] == 0:
+            raise ValueError(f"GpuFinetuneLoader: clip {name!r} has an empty window (grid='window' sizes the grid from the window's rows)")
+        x0, x1, y0, y1 = window[:, 0].min(), window[:, 0].max(), window[:, 1].min(), window[:, 1].max()
+        if not (x0 >= 0 and y0 >= 0):
+            raise ValueError(f"GpuFinetuneLoader: clip {name!r} has a negative coordinate (min x {x0}, min y {y0})")
+        if not (x1 < cap_w and y1 < cap_h):
+            raise ValueError(f"GpuFinetuneLoader: clip {name!r} reaches past the capacity {cap_h} x {cap_w} (max x {x1}, max y {y1})")
+
+    def _geometry_checked(self):
+        """End of a pass with grid="window": the device's count of refused windows, read once (the host check above should leave it 0)."""
+        if self.geom_status is None:
+            return
+        bad = int(self.geom_status.item())
+        if bad:
+            self.geom_status.zero_()
+            raise ValueError(f"GpuFinetuneLoader: evp_events_window_geometry refused {bad} window(s) of this pass (empty, a negative coordinate, "
+                             f"or an extent above the capacity {self.sensor[0]} x {self.sensor[1]}); their grids were clamped")
 
     def __iter__(self):
         if not self.is_train:
@@ -112,6 +158,9 @@ class GpuFinetuneLoader(ClipWindowLoader):
             else:
                 # algo 3: float64 cells in K1's LDS tile -- the sum no longer depends on the order its atomics arrive in, so a pass repeats
                 # bit for bit (the float32 cells of the default differ by an ulp or two from launch to launch); 1.2 x the K1 time
+                if self.window:
+                    call("evp_events_window_geometry", ptr(self.ev), ptr(self.d_off), ptr(self.d_off[1:]), self.B, self.sensor[0], self.sensor[1], 0,
+                         1.0, 0, 0, 0, None, ptr(self.ext), ptr(self._full), ptr(self.geom_status), stream_ptr())
                 vox = voxel_grid_batch(self.ev[:n], self.d_off, self.bins, self.grid_hw, scale=self.scale,
                                        out=self.out if self.raw is None else self.raw, algo=3)
                 if self.raw is not None:
@@ -120,3 +169,4 @@ class GpuFinetuneLoader(ClipWindowLoader):
             yield {"events_voxel_grid": vox, "label": self._lab[slot], "image_name": names}
             # the consumer has queued its step: what reads the grids, the labels and (before it) the event buffer is on its stream now
             self._mark_read(torch.cuda.current_stream(self.dev))
+        self._geometry_checked()

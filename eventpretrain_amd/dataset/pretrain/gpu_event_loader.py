@@ -68,6 +68,9 @@ class ClipWindowLoader:
     def _upload_extra(self, slot):
         pass
 
+    def _check_window(self, window, name):
+        pass
+
     def _pack(self, it, slot, step):
         """Host half of one batch (worker thread): B samples -> their windows in the pinned slot. `step`: the counter stream's step of
         THIS batch (the pack runs one batch ahead). -> (rows, names) or None at the end of the pass."""
@@ -88,6 +91,7 @@ class ClipWindowLoader:
                 raise ValueError(f"{type(self).__name__}: events must be float64 [n,4] (x,y,t,p)")
             s0 = (int(w0[i]) * (e.shape[0] - fix)) >> 32 if e.shape[0] > fix else 0
             k = min(e.shape[0], fix)
+            self._check_window(e[s0:s0 + k], name)
             ev_h[n:n + k] = e[s0:s0 + k]
             n += k
             off_h[i + 1] = n

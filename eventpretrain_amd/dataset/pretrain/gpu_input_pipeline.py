@@ -37,7 +37,11 @@ dataset.pretrain.gpu_event_loader.GpuEventLoader puts that chain at the DataLoad
 
 Recipe keywords (constructor; the defaults are the pre-training chain above): `grid="sensor"` voxelises the UNSCALED events at the
 sensor's (H, W) and lets the view stage resize H x W -> S x S, the crop rows drawn on the H x W grid (five of the reference's
-classification fine-tuning datasets); `sensor`, `fix_events_num` override the namespace's fields; `view_augment=False` makes the view stage
+classification fine-tuning datasets); `grid="window"` (N-Cars, ft_n_cars_dataset.py:61-87) gives every clip a grid of its own, H_c = int(max y)
++ 1 by W_c = int(max x) + 1 over the rows of its picked window: `sensor` is then the CAPACITY (cap_h, cap_w) of the padded grid K1 and the
+view kernels run at, and a kernel of the captured self-driven chain (evp_events_window_geometry) measures each window, draws the crop row
+on the clip's own grid and hands the extent to the added-row build (evp_events_build_added_hw_f64) -- that chain is the only way to run
+it; `sensor`, `fix_events_num` override the namespace's fields; `view_augment=False` makes the view stage
 view_resize alone (the validation recipe); `voxel_cells="f64"` bins the captured chain's fused K1 with float64 LDS cells
 (evp_voxel_scatter_fused_algo_f32, algo 3), whose grids repeat bit for bit from launch to launch."""
 from concurrent.futures import ThreadPoolExecutor
@@ -70,14 +74,17 @@ class GpuInputPipeline:
         Neither are the recipe keywords:
         `grid`: "input" (N-ImageNet: events_reshape to input_size, voxelise at S x S, crop rows drawn on S x S) or "sensor" (N-Caltech101,
         CIFAR10-DVS, DVS128-Gesture, UCF101-DVS, ES-ImageNet with 5 bins, ft_n_caltech101_dataset.py:61-91: voxelise the unscaled events at
-        the sensor's (H, W), crop rows drawn on H x W, the view stage resizes H x W -> S x S).
+        the sensor's (H, W), crop rows drawn on H x W, the view stage resizes H x W -> S x S) or "window" (N-Cars: as "sensor", but on each
+        clip's own H_c x W_c inside a padded grid of the capacity `sensor`; the captured self-driven chain only, run / prepare / batch refuse).
         `sensor`: (h, w) in place of (args.img_sensor_h, args.img_sensor_w). `fix_events_num`: in place of args.fix_events_num (window
         length, bound of the erase / add counts). `view_augment=False`: the view stage is view_resize alone -- the constant row
         (0, 0, W, H, 0, 0) for every clip, and no resize at all where the grid already has the view's size (the validation recipe).
         `voxel_cells`: the captured chain's fused K1 accumulates in "f32" or "f64" LDS cells (evp_voxel_scatter_fused_algo_f32 algo 0 / 3)."""
         self.RING = int(ring)
-        if grid not in ("input", "sensor"):
-            raise ValueError(f"grid must be 'input' or 'sensor' (got {grid!r})")
+        if grid not in ("input", "sensor", "window"):
+            raise ValueError(f"grid must be 'input', 'sensor' or 'window' (got {grid!r})")
+        if grid == "window" and sensor is None:
+            raise ValueError("grid='window' needs sensor=(cap_h, cap_w), the capacity of the padded grid")
         if voxel_cells not in ("f32", "f64"):
             raise ValueError(f"voxel_cells must be 'f32' or 'f64' (got {voxel_cells!r})")
         self.grid, self.voxel_cells, self.view_augment = grid, voxel_cells, bool(view_augment)
@@ -96,10 +103,18 @@ class GpuInputPipeline:
         # the grid K1 bins at, and the x / y scale it applies: the input's size after events_reshape, or the sensor's own
         self.gh, self.gw = (self.S, self.S) if grid == "input" else self.sensor
         self.scale = (self.S / self.sensor[1], self.S / self.sensor[0]) if grid == "input" else (1.0, 1.0)
+        # is the view stage a real resize? (view_resize of an S x S grid to S x S is the identity; a window grid always differs from its capacity)
+        self.resize = self.view_augment or (self.gh, self.gw) != (self.S, self.S) or grid == "window"
         self._full_rows = {}
         self.bins = int(args.num_bins)
         self.crop_min = float(getattr(args, "crop_min", 0.8))
         self._pins, self._busy, self._turn, self._pool = [None] * self.RING, [None] * self.RING, 0, None
+
+    def _captured_only(self, what):
+        """grid="window": the per-clip extents exist on the device alone (evp_events_window_geometry inside the captured chain)."""
+        if self.grid == "window":
+            raise ValueError(f"GpuInputPipeline.{what}: grid='window' runs in the captured self-driven chain only (capture(..., clip_offsets=...), "
+                             "fused_voxel=True): this path bounds the added rows through scalar arguments and draws crop rows from sizes alone")
 
     def full_rows(self, n_clips, device):
         """The view stage's rows without view augmentation: (0, 0, W, H, 0, 0) per clip, a static device tensor (view_resize alone)."""
@@ -192,6 +207,7 @@ class GpuInputPipeline:
         """events float64 CUDA [n_total,4] (x,y,t,p) sensor coordinates, clips time-sorted; clip_offsets int64 host [B+1].
         `frame_params`: the frames' own rows (see draw); default = `params` (frames of the grid's size).
         Returns (voxels float32 [B,bins,S,S], targets float32 [B,C,S,S] | None)."""
+        self._captured_only("run")
         _lib.require_device()
         H, W = self.sensor
         if self.stream == "device" and isinstance(decisions, tuple) and len(decisions) == 2 and isinstance(decisions[0], np.ndarray):
@@ -221,6 +237,7 @@ class GpuInputPipeline:
     def prepare(self, clip_offsets, step, first_sample=0, sample_seeds=None, frame_size=None):
         """Host work of one batch (decisions, range checks, packing into a pinned slot). Thread-safe with respect to the device:
         touches no stream except to wait for the slot's previous upload."""
+        self._captured_only("prepare")
         offs = np.asarray(clip_offsets, dtype=np.int64)
         n_clips = offs.shape[0] - 1
         drawn = self.draw(offs[1:] - offs[:-1], step, first_sample, sample_seeds, frame_size=frame_size)
@@ -305,6 +322,7 @@ class GpuInputPipeline:
     def run_prepared(self, events, pb, frames=None, assume_sorted=True):
         """Device half: ONE upload of the packed tables, then erase / add merge (2 launches), K1 with the sensor -> input rescale (3),
         view augmentation (1) and the target's frame augmentation (1). No host read-back, no per-batch host arithmetic."""
+        self._captured_only("run_prepared")
         _lib.require_device()
         if not events.is_cuda or events.dtype != torch.float64 or events.dim() != 2 or events.shape[1] != 4 or not events.is_contiguous():
             raise _lib.EvpError("run_prepared: events must be a contiguous float64 [N,4] tensor in device memory")
@@ -377,6 +395,7 @@ class GpuInputPipeline:
 
     def batch(self, events, clip_offsets, step, frames=None, first_sample=0, sample_seeds=None):
         """The whole chain for one batch: decisions on the host, data on the device."""
+        self._captured_only("batch")
         if self.stream == "device":
             offs = np.asarray(clip_offsets.cpu() if torch.is_tensor(clip_offsets) else clip_offsets, dtype=np.int64)
             pb = self.prepare(offs, step, first_sample, sample_seeds, frame_size=None if frames is None else frames.shape[-2:])
@@ -399,7 +418,7 @@ class GpuInputPipeline:
         n = float(np.sum(sizes))
         grid = self.bins * self.gh * self.gw * 4.0 * len(sizes)           # the raw grids (the sensor's size with grid="sensor")
         view = self.bins * self.S * self.S * 4.0 * len(sizes)
-        resize = self.view_augment or (self.gh, self.gw) != (self.S, self.S)      # no view kernel where view_resize is the identity
+        resize = self.resize                                                       # no view kernel where view_resize is the identity
         if fused:
             if not resize:
                 return n * 32 + view
@@ -415,6 +434,10 @@ class CapturedChain:
         if pipe.stream != "device":
             raise ValueError("CapturedChain needs decision_stream='device' (host-drawn decision lists change size per batch)")
         _lib.require_device()
+        self.window = pipe.grid == "window"
+        if self.window and (clip_offsets is None or not fused_voxel or frames is not None):
+            raise ValueError("CapturedChain: grid='window' runs in the captured self-driven chain only: capture with clip_offsets, "
+                             "fused_voxel=True and no frames")
         self.pipe, self.events, self.frames, self.nc = pipe, events, frames, n_clips
         dev = events.device
         fix = self.fix = pipe.fix
@@ -429,13 +452,18 @@ class CapturedChain:
         self.nz = torch.zeros(n_clips * self.kmax * 3, dtype=torch.float64, device=dev)
         self.ws = torch.zeros(n_clips * self.kmax, 4, dtype=torch.float64, device=dev)
         self.fused = bool(fused_voxel) and fix <= 48 * 1024 * 8
+        if self.window and not self.fused:
+            raise ValueError(f"CapturedChain: grid='window' runs in the captured self-driven chain's fused form only (fix_events_num {fix} is too long for it)")
         self.ev = None if self.fused else torch.zeros(n_clips * (fix + self.kmax), 4, dtype=torch.float64, device=dev)
         self.kws = torch.zeros(n_clips * (pipe.bins + 5), dtype=torch.int64, device=dev) if self.fused else None
         # bilinear mode: an output row blends two grid rows, and the pair that straddles K1's LDS tile boundary is summed by two
         # workgroups, so the resize cannot ride on the tile flush -- the fused K1 stops at the raw grids (kept here, static, for whoever
         # wants to look at them) and evp_view_augment_bilinear_f32 follows on the same stream
         # (no view stage at all -- view_augment=False on a grid of the view's size -- needs no raw grids in either mode: K1 writes `out`)
-        self.resize = pipe.view_augment or (pipe.gh, pipe.gw) != (pipe.S, pipe.S)
+        self.resize = pipe.resize
+        # grid="window": each clip's extent (H_c, W_c) of this batch and the count of refused windows (see _launches)
+        self.ext = torch.zeros(n_clips, 2, dtype=torch.int32, device=dev) if self.window else None
+        self.geom_status = torch.zeros(1, dtype=torch.int32, device=dev) if self.window else None
         self.raw = (torch.zeros(n_clips, pipe.bins, pipe.gh, pipe.gw, dtype=torch.float32, device=dev)
                     if self.fused and self.resize and pipe.resize_mode != "nearest" else None)
         self.algo = 3 if pipe.voxel_cells == "f64" else 0
@@ -466,6 +494,8 @@ class CapturedChain:
             self.out, self.tgt = self._launches()
         if self.self_driven:
             self.set_state(0, 0)                      # the warm-up advanced it
+        if self.window:
+            self.geom_status.zero_()                  # (a warm-up on offsets that are still zero counts B empty windows)
 
     def set_clip_offsets(self, clip_offsets):
         """Self-driven chain: the clip offsets of the rows now in the event buffer (int64 [n_clips + 1], host or device). Every clip's
@@ -507,15 +537,25 @@ class CapturedChain:
                  float(pipe.crop_min), ptr(tabs), ptr(d[o4:]), None if fr is None else ptr(d[o4 + pw:]), stream_ptr())
         else:
             d.copy_(self.h_tab, non_blocking=True)        # an upload node of the graph
+        if self.window:
+            # each clip's own grid (H_c, W_c) from its window's rows, and the crop row drawn ON that grid (view_augment=False: the clip's
+            # full box) written over the plan's row for the capacity; the layout of d_tab stays as it is
+            call("evp_events_window_geometry", ptr(self.events), ptr(tabs[0]), ptr(tabs[1]), nc, pipe.gh, pipe.gw, int(pipe.view_augment),
+                 float(pipe.crop_min), pipe.seed & (2 ** 64 - 1), 0, 0, ptr(d[self.n_tab:]), ptr(self.ext), ptr(d[o4:]), ptr(self.geom_status),
+                 stream_ptr())
         call("evp_events_draw_erase_add", ptr(tabs[0]), ptr(tabs[1]), nc, ptr(tabs[2]), ptr(tabs[3]), pipe.seed & (2 ** 64 - 1), 0, 0,
              ptr(d[self.n_tab:]), self.kmax, ptr(self.er), ptr(self.ai), ptr(self.nz), stream_ptr())
         if self.fused:
             # the added rows built and time-sorted (in the draw kernel's add workgroup they buy nothing: 261 vs 262 us per batch), then the
             # grids straight from window rows + erase list + added rows (no merged clip) ...
-            call("evp_events_build_added_f64", ptr(self.events), ptr(tabs[0]), nc, ptr(self.ai), ptr(self.nz), ptr(tabs[3]), self.kmax, float(W),
-                 float(H), ptr(self.ws), stream_ptr())
+            if self.window:                           # ... clipped to the clip's own (H_c, W_c)
+                call("evp_events_build_added_hw_f64", ptr(self.events), ptr(tabs[0]), nc, ptr(self.ai), ptr(self.nz), ptr(tabs[3]), self.kmax, float(W),
+                     float(H), ptr(self.ext), ptr(self.ws), stream_ptr())
+            else:
+                call("evp_events_build_added_f64", ptr(self.events), ptr(tabs[0]), nc, ptr(self.ai), ptr(self.nz), ptr(tabs[3]), self.kmax, float(W),
+                     float(H), ptr(self.ws), stream_ptr())
             # ... and they leave through the view augmentation (crop / nearest resize / flips), so the raw grids are never stored either
-            p_dev = d[o4:o4 + pw].view(torch.int32)[:nc * 6].view(nc, 6) if pipe.view_augment else pipe.full_rows(nc, d.device)
+            p_dev = d[o4:o4 + pw].view(torch.int32)[:nc * 6].view(nc, 6) if pipe.view_augment or self.window else pipe.full_rows(nc, d.device)
             sx, sy = pipe.scale
             fused_args = (ptr(self.events), ptr(tabs[0]), ptr(tabs[1]), nc, ptr(self.er), ptr(tabs[2]), ptr(self.ws), ptr(tabs[3]), self.fix, pipe.bins,
                           pipe.gh, pipe.gw, sx, sy)

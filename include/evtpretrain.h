@@ -32,7 +32,7 @@ enum { EVP_ACT_NONE = 0, EVP_ACT_GELU = 1, EVP_ACT_DGELU = 2, EVP_ACT_RELU = 3, 
 const char *evp_last_error(void);
 /* ABI version of this header; bumped on any signature change (2: evp_dropout_fwd takes a device-side seed; evp_gemm_desc lost its
  * stream-K workspace fields in round 3; 3: evp_events_draw_erase_add; 4: keep flags on the window attention; 5: evp_events_plan_batch; entries ADDED since -- evp_cls_metrics,
- * evp_view_augment_bilinear_f32, evp_voxel_scatter_fused_algo_f32 -- change no signature and keep 5). A host binding must compare evp_abi_version() with EVP_ABI_VERSION at load time. */
+ * evp_view_augment_bilinear_f32, evp_voxel_scatter_fused_algo_f32, evp_events_window_geometry, evp_events_build_added_hw_f64 -- change no signature and keep 5). A host binding must compare evp_abi_version() with EVP_ABI_VERSION at load time. */
 #define EVP_ABI_VERSION 5
 int evp_abi_version(void);
 /* Name of the code object's target ("gfx950"). */
@@ -98,6 +98,25 @@ int evp_events_erase_add_win_f64(const double *events, const int64_t *win_begin,
 int evp_events_build_added_f64(const double *events, const int64_t *win_begin, int n_clips, const int64_t *add_idx, const double *add_noise,
                                const int64_t *add_offsets, int max_add_per_clip, double sensor_w, double sensor_h, double *add_rows,
                                void *stream);
+/* The same with a per-clip bound (N-Cars, ft_n_cars_dataset.py:64-70: events_augment(size=(H_c, W_c)) with the window's own extent): with
+ * clip_hw (device int32 [n_clips,2] = (H_c, W_c), as evp_events_window_geometry writes it) clip c's rows are clipped to [0, W_c - 1] x
+ * [0, H_c - 1]; with clip_hw == NULL to the two scalars -- evp_events_build_added_f64, which forwards here. One kernel body. */
+int evp_events_build_added_hw_f64(const double *events, const int64_t *win_begin, int n_clips, const int64_t *add_idx, const double *add_noise,
+                                  const int64_t *add_offsets, int max_add_per_clip, double sensor_w, double sensor_h, const int32_t *clip_hw,
+                                  double *add_rows, void *stream);
+/* Per-clip window GEOMETRY (N-Cars, ft_n_cars_dataset.py:61-87): clip c = rows [win_begin[c], win_end[c]) of `events` (float64 [.,4]
+ * x,y,t,p, 16-byte aligned; int64 [n_clips] absolute rows each) gets clip_hw[c] = (H_c, W_c) = (int(max y) + 1, int(max x) + 1) over its
+ * window and params[c] (int32 [n_clips,6]): with draw_crop the row evg_augment draws on an H_c x W_c view -- the 52 uniforms of purpose 4
+ * keyed by (seed, step, first_sample + c) that evp_events_plan_batch draws, its crop arithmetic, the geometry computed per clip in double;
+ * step_first_dev (optional, device int64[2]) overrides (step, first_sample) as in evp_events_draw_erase_add -- without draw_crop
+ * (0, 0, W_c, H_c, 0, 0): view_resize alone. (cap_h, cap_w) is the CAPACITY: the size of the padded grid K1 and the view kernels run at,
+ * of which the clip fills the top-left H_c x W_c. A window that is empty, holds a negative coordinate or has an extent above the capacity
+ * is refused: its extent is clamped into [1, cap] and *status (device int32, accumulated: the caller zeroes it) grows by one per such
+ * clip; nothing is read or written out of bounds. One workgroup per clip, one launch. Host-side refusals before any launch: null pointers
+ * and crop_min outside (0, 1] EVP_EINVAL; n_clips <= 0 and a capacity <= 0 EVP_ESHAPE. */
+int evp_events_window_geometry(const double *events, const int64_t *win_begin, const int64_t *win_end, int n_clips, int cap_h, int cap_w,
+                               int draw_crop, double crop_min, uint64_t seed, uint64_t step, int64_t first_sample,
+                               const int64_t *step_first_dev, int32_t *clip_hw, int32_t *params, int32_t *status, void *stream);
 /* The DECISIONS of erase_and_add_events drawn on the device (events_augment.py:31-44: which rows to erase, which to copy, the three
  * normal noise columns of the copies): clip c (rows [win_begin[c], win_end[c]) of some event array, n_c of them) gets
  * erase_offsets[c+1] - erase_offsets[c] DISTINCT rows in erase_idx (ascending, clip-relative) and add_offsets[c+1] - add_offsets[c]
