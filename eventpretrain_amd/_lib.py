@@ -125,6 +125,16 @@ SIGNATURES = {
     "evp_cls_metrics": [_vp, _vp, _i64, _i, _i64, _vp, _vp, _i64, _vp, _vp],
     "evp_dropout_fwd": [_vp, _i, _vp, _vp, _i64, _f, C.c_uint64, _vp, C.c_uint64, _vp],
     "evp_dropout_apply": [_vp, _i, _vp, _vp, _i64, _f, _vp],
+    "evp_im2col3x3": [_vp, _i, _i64, _i, _i, _i, _i, _vp, _i, _i64, _vp],
+    "evp_col2im3x3": [_vp, _i, _i64, _i, _i, _i, _i, _vp, _i, _i64, _i64, _vp],
+    "evp_adaptive_avgpool_fwd": [_vp, _i, _i64, _i, _i, _i, _i, _i, _vp, _i, _i64, _i64, _vp],
+    "evp_adaptive_avgpool_bwd": [_vp, _i, _i64, _i, _i, _i, _i, _i, _vp, _i, _i64, _i64, _vp],
+    "evp_upsample_bilinear_fwd": [_vp, _i, _i64, _i, _i, _i, _i, _i, _i, _vp, _i, _i64, _i64, _vp],
+    "evp_upsample_bilinear_bwd": [_vp, _i, _i64, _i, _i, _i, _i, _i, _i, _vp, _i, _i64, _i64, _vp],
+    "evp_channel_scale": [_vp, _i, _i64, _vp, _i, _i, _i, _vp, _i, _i64, _i64, _vp],
+    "evp_batchnorm_eval": [_vp, _i, _i64, _i64, _i, _vp, _vp, _vp, _vp, _f, _i, _vp, _i, _i64, _i64, _vp],
+    "evp_batchnorm_eval_bwd": [_vp, _i, _i64, _vp, _i, _i64, _i64, _i, _vp, _vp, _f, _i, _vp, _i, _i64, _vp],
+    "evp_colsum_ordered":[_vp, _i, _i64, _i, _i64, _vp, _vp],
     "evp_abi_version": [],
 }
 _OTHER_RESTYPE = {"evp_last_error": C.c_char_p, "evp_target_arch": C.c_char_p}

@@ -1808,3 +1808,319 @@ def cls_metrics(pred, label, table, cursor):
     ws = torch.empty(_lib.CLS_METRICS_WS, dtype=torch.float32, device=pred.device) if R > _lib.CLS_METRICS_SINGLE_ROWS else None
     call("evp_cls_metrics", pred.data_ptr(), ptr(_chk(label, torch.int64)), R, n_cls, ld, ptr(_chk(cursor, torch.int64)),
          ptr(_chk(table, torch.float32)), table.shape[0], ptr(ws), stream_ptr())
+
+
+# ----------------------------------------------------------------------------------------------------- dense-prediction heads
+# csrc/dense.hip. A "map" is a token-major 2-D tensor [B*H*W, C] whose rows may be further apart than C (a channel slice of a wider
+# buffer). `out=(buf, off)`: the op writes its C columns into buf[:, off:off+C] and returns that slice, so the reference's
+# torch.cat(dim=1) becomes one buffer its producers fill (CatFn).
+def _map(t, what="map"):
+    """-> (tensor, leading dimension in elements) of a token-major map."""
+    if not t.is_cuda:
+        raise _lib.EvpError(f"{what} is not in device memory; eventpretrain_amd has no CPU path")
+    if t.dim() != 2:
+        raise _lib.EvpError(f"{what} must be a 2-D tensor (got shape {tuple(t.shape)})")
+    if t.shape[1] > 1 and t.stride(1) != 1:
+        t = t.contiguous()           # a gradient that arrives channel-major (through the NCHW permute of a prediction)
+    return t, (t.stride(0) if t.shape[0] > 1 else max(t.stride(0), t.shape[1]))
+
+
+def _slot(out, R, C, dtype, device):
+    """-> (buffer, ld, column offset, the [R, C] view the caller returns) of an output given as None or (buf, off)."""
+    if out is None:
+        buf = torch.empty(R, C, dtype=dtype, device=device)
+        return buf, C, 0, buf
+    buf, off = out
+    if buf.dim() != 2 or not buf.is_contiguous() or buf.shape[0] != R or off < 0 or off + C > buf.shape[1]:
+        raise _lib.EvpError(f"output slot [{R}, {off}:{off + C}] does not fit a buffer of shape {tuple(buf.shape)}")
+    return buf, buf.shape[1], off, buf[:, off:off + C]
+
+
+def map_copy(x, dtype, out=None, scale=None, rows_per_sample=None):
+    """Strided cast-copy of a map (evp_channel_scale), times scale[b, c] when given (float32 [B, C], rows_per_sample rows per b)."""
+    x, ldi = _map(x)
+    R, Cc = x.shape
+    buf, ldo, off, view = _slot(out, R, Cc, dtype, x.device)
+    Bn, P = (1, R) if scale is None else (R // rows_per_sample, rows_per_sample)
+    call("evp_channel_scale", ptr(x), dt(x), ldi, ptr(scale), Bn, P, Cc, ptr(buf), dt(buf), ldo, off, stream_ptr())
+    return view
+
+
+def _contig(x, dtype):
+    """A contiguous [R, C] copy of a map in `dtype`, or the map itself where it already is one."""
+    if x.dtype == dtype and x.is_contiguous():
+        return x
+    return map_copy(x, dtype)
+
+
+def colsum_ordered(x):
+    x, ld = _map(x)
+    out = torch.empty(x.shape[1], dtype=torch.float32, device=x.device)
+    call("evp_colsum_ordered", ptr(x), dt(x), x.shape[0], x.shape[1], ld, ptr(out), stream_ptr())
+    return out
+
+
+def im2col3x3(x, B, H, W):
+    x, ldi = _map(x)
+    Cc = x.shape[1]
+    cols = torch.empty(B * H * W, Cc * 9, dtype=_compute_dtype, device=x.device)
+    call("evp_im2col3x3", ptr(x), dt(x), ldi, B, H, W, Cc, ptr(cols), dt(cols), Cc * 9, stream_ptr())
+    return cols
+
+
+class MapCopyFn(torch.autograd.Function):
+    """A map in another element type and / or in its slice of a concat buffer; the gradient comes back in the input's type."""
+
+    @staticmethod
+    def forward(ctx, x, dtype, out):
+        ctx.xdt = x.dtype
+        return map_copy(x.detach(), dtype, out)
+
+    @staticmethod
+    def backward(ctx, g):
+        return _contig(g, ctx.xdt), None, None
+
+
+class CatFn(torch.autograd.Function):
+    """torch.cat(maps, dim=1) where every map already IS its slice of `buf` (the ops' `out=(buf, off)`): nothing moves. Backward hands
+    each producer its columns of the gradient, as a strided view."""
+
+    @staticmethod
+    def forward(ctx, holder, *views):
+        (buf,), off = holder, 0
+        for v in views:
+            if v.data_ptr() != buf.data_ptr() + off * buf.element_size() or v.stride(0) != buf.stride(0) or v.dtype != buf.dtype:
+                raise _lib.EvpError("CatFn: a map is not the slice of the buffer it stands for")
+            off += v.shape[1]
+        if off != buf.shape[1]:
+            raise _lib.EvpError("CatFn: the maps do not fill the buffer")
+        ctx.widths = [v.shape[1] for v in views]
+        return buf.view(buf.shape)
+
+    @staticmethod
+    def backward(ctx, g):
+        outs, off = [], 0
+        for w in ctx.widths:
+            outs.append(g[:, off:off + w])
+            off += w
+        return (None, *outs)
+
+
+class ConvBNFn(torch.autograd.Function):
+    """The reference's ConvModule (ft_dense_decoder.py:7-20) on a token-major map: Conv2d(kernel 1 or 3, stride 1, padding k // 2, with
+    bias) -> BatchNorm2d -> ReLU. The convolution is a GEMM on the map's rows (k = 1) or on their 3x3 patch rows (evp_im2col3x3), the
+    bias in its epilogue: it sits in front of the normalisation, so it moves running_mean and its gradient is the column sum of the
+    pre-BN gradient (zero up to rounding in training mode). training: batch statistics over the B*H*W rows, running statistics updated
+    in place; else evp_batchnorm_eval on the running statistics (no gradients for the BatchNorm affine parameters then)."""
+
+    @staticmethod
+    def forward(ctx, x, w, b, gamma, beta, running_mean, running_var, B, H, W, eps, momentum, relu, training, out):
+        T = _compute_dtype
+        R, N, k = B * H * W, w.shape[0], w.shape[-1]
+        if k not in (1, 3) or w.shape[-2] != k:
+            raise NotImplementedError("ConvBNFn: kernel size 1 or 3")
+        if training and R == 1:
+            raise ValueError(f"Expected more than 1 value per channel when training, got input size {[B, N, H, W]}")
+        dev = x.device
+        xd = x.detach()
+        a = _contig(xd, T) if k == 1 else im2col3x3(xd, B, H, W)
+        K = a.shape[1]
+        wl = lp_weight(w).view(N, K)
+        y_pre = torch.empty(R, N, dtype=T, device=dev)
+        gemm(a, wl, y_pre, M=R, N=N, K=K, bias=b)
+        if training:
+            y = torch.empty(R, N, dtype=T, device=dev)
+            mean = torch.empty(N, dtype=torch.float32, device=dev)
+            invstd = torch.empty(N, dtype=torch.float32, device=dev)
+            ws = torch.empty((2 * call("evp_batchnorm_nblk", R) + 2) * N, dtype=torch.float32, device=dev)
+            call("evp_batchnorm_fwd", ptr(y_pre), dt(y_pre), R, N, ptr(gamma), ptr(beta), float(eps), float(momentum), int(relu),
+                 ptr(y), ptr(mean), ptr(invstd), ptr(running_mean), ptr(running_var), ptr(ws), stream_ptr())
+            ret = y if out is None else map_copy(y, T, out)
+            ctx.save_for_backward(a, wl, y_pre, y, mean, invstd, gamma)
+        else:
+            buf, ldo, off, ret = _slot(out, R, N, T, dev)
+            call("evp_batchnorm_eval", ptr(y_pre), dt(y_pre), N, R, N, ptr(gamma), ptr(beta), ptr(running_mean), ptr(running_var),
+                 float(eps), int(relu), ptr(buf), dt(buf), ldo, off, stream_ptr())
+            ctx.save_for_backward(a, wl, ret, running_var.clone(), gamma)
+        ctx.cfg = (B, H, W, k, bool(relu), bool(training), float(eps), x.dtype, x.requires_grad)
+        ctx.prm = (w, b)
+        return ret
+
+    @staticmethod
+    def backward(ctx, g):
+        B, H, W, k, relu, training, eps, xdt, need_dx = ctx.cfg
+        w, b = ctx.prm
+        R, dev = B * H * W, g.device
+        dgamma = dbeta = None
+        if training:
+            a, wl, y_pre, y, mean, invstd, gamma = ctx.saved_tensors
+            N = y.shape[1]
+            gc = _contig(g, y.dtype)
+            dpre = torch.empty(R, N, dtype=y.dtype, device=dev)
+            ws = torch.empty((2 * call("evp_batchnorm_nblk", R) + 2) * N, dtype=torch.float32, device=dev)
+            dgamma = torch.empty(N, dtype=torch.float32, device=dev)
+            dbeta = torch.empty(N, dtype=torch.float32, device=dev)
+            call("evp_batchnorm_bwd", ptr(gc), ptr(y_pre), ptr(y), dt(y), R, N, ptr(gamma), ptr(mean), ptr(invstd), int(relu),
+                 ptr(dpre), ptr(dgamma), ptr(dbeta), ptr(ws), stream_ptr())
+        else:
+            a, wl, y, rvar, gamma = ctx.saved_tensors
+            N = y.shape[1]
+            gm, ldg = _map(g)
+            ym, ldy = _map(y)
+            dpre = torch.empty(R, N, dtype=y.dtype, device=dev)
+            call("evp_batchnorm_eval_bwd", ptr(gm), dt(gm), ldg, ptr(ym), dt(ym), ldy, R, N, ptr(gamma), ptr(rvar), eps, int(relu),
+                 ptr(dpre), dt(dpre), N, stream_ptr())
+        K = a.shape[1]
+        db = colsum_ordered(dpre) if (b is not None and ctx.needs_input_grad[2]) else None
+        dw = _wgrad(dpre, a, N, K, R, w, shape=tuple(w.shape)) if ctx.needs_input_grad[1] else None
+        dx = None
+        if need_dx:
+            if k == 1:
+                dx = torch.empty(R, K, dtype=xdt, device=dev)
+                gemm(dpre, wl, dx, M=R, N=K, K=N, trans_b=True, ldb=K)
+            else:
+                Cin = K // 9
+                dcols = torch.empty(R, K, dtype=dpre.dtype, device=dev)
+                gemm(dpre, wl, dcols, M=R, N=K, K=N, trans_b=True, ldb=K)
+                dx = torch.empty(R, Cin, dtype=xdt, device=dev)
+                call("evp_col2im3x3", ptr(dcols), dt(dcols), K, B, H, W, Cin, ptr(dx), dt(dx), Cin, 0, stream_ptr())
+        return (dx, dw, db, dgamma, dbeta) + (None,) * 10
+
+
+def conv_bn_map(x, conv, bn, B, H, W, relu=True, out=None):
+    """One ConvModule on a map: the parameters and buffers of (nn.Conv2d, nn.BatchNorm2d), the module's training flag, and the
+    num_batches_tracked count torch keeps."""
+    if conv.stride != (1, 1) or conv.dilation != (1, 1) or conv.groups != 1 or conv.padding != (conv.kernel_size[0] // 2,) * 2:
+        raise NotImplementedError("conv_bn_map: stride 1, dilation 1, padding k // 2 only")
+    y = ConvBNFn.apply(x, conv.weight, conv.bias, bn.weight, bn.bias, bn.running_mean, bn.running_var, B, H, W, bn.eps,
+                       0.1 if bn.momentum is None else bn.momentum, relu, bn.training, out)
+    if bn.training and bn.num_batches_tracked is not None:
+        bn.num_batches_tracked += 1
+    return y
+
+
+class AdaptivePoolFn(torch.autograd.Function):
+    """nn.AdaptiveAvgPool2d(s) on a map [B*H*W, C] -> [B*s*s, C] in the compute dtype."""
+
+    @staticmethod
+    def forward(ctx, x, B, H, W, s):
+        xm, ldi = _map(x.detach())
+        Cc = xm.shape[1]
+        out = torch.empty(B * s * s, Cc, dtype=_compute_dtype, device=x.device)
+        call("evp_adaptive_avgpool_fwd", ptr(xm), dt(xm), ldi, B, H, W, Cc, s, ptr(out), dt(out), Cc, 0, stream_ptr())
+        ctx.cfg = (B, H, W, Cc, s, x.dtype)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        B, H, W, Cc, s, xdt = ctx.cfg
+        gm, ldg = _map(g)
+        dx = torch.empty(B * H * W, Cc, dtype=xdt, device=g.device)
+        call("evp_adaptive_avgpool_bwd", ptr(gm), dt(gm), ldg, B, H, W, Cc, s, ptr(dx), dt(dx), Cc, 0, stream_ptr())
+        return dx, None, None, None, None
+
+
+class UpsampleBilinearFn(torch.autograd.Function):
+    """F.interpolate(size=(H, W), mode="bilinear", align_corners=False) on a map [B*h*w, C] -> [B*H*W, C] (the input's element type,
+    or the slot's)."""
+
+    @staticmethod
+    def forward(ctx, x, B, h, w, H, W, out):
+        xm, ldi = _map(x.detach())
+        Cc = xm.shape[1]
+        buf, ldo, off, view = _slot(out, B * H * W, Cc, xm.dtype, x.device)
+        call("evp_upsample_bilinear_fwd", ptr(xm), dt(xm), ldi, B, h, w, H, W, Cc, ptr(buf), dt(buf), ldo, off, stream_ptr())
+        ctx.cfg = (B, h, w, H, W, Cc, x.dtype)
+        return view
+
+    @staticmethod
+    def backward(ctx, g):
+        B, h, w, H, W, Cc, xdt = ctx.cfg
+        gm, ldg = _map(g)
+        dx = torch.empty(B * h * w, Cc, dtype=xdt, device=g.device)
+        call("evp_upsample_bilinear_bwd", ptr(gm), dt(gm), ldg, B, h, w, H, W, Cc, ptr(dx), dt(dx), Cc, 0, stream_ptr())
+        return (dx,) + (None,) * 6
+
+
+def resize_map(x, B, h, w, H, W, mode="bilinear", out=None):
+    """The reference's resize() between two map sizes; at equal size the map itself."""
+    if mode != "bilinear":
+        raise NotImplementedError(f"sample_mode {mode!r}: only 'bilinear' (what both of the reference's entry scripts set)")
+    if (h, w) == (H, W):
+        return x if out is None else MapCopyFn.apply(x, _compute_dtype, out)
+    return UpsampleBilinearFn.apply(x, B, h, w, H, W, out)
+
+
+class ChannelDropoutFn(torch.autograd.Function):
+    """nn.Dropout2d on a map: out[(b,p), c] = x[(b,p), c] * scale[b, c] with scale in {0, 1/(1-p)} (float32 [B, C]); the output is
+    the compute-dtype operand of the classifier GEMM. The backward is the same kernel."""
+
+    @staticmethod
+    def forward(ctx, x, scale, rows_per_sample):
+        ctx.save_for_backward(scale)
+        ctx.cfg = (rows_per_sample, x.dtype)
+        return map_copy(x.detach(), _compute_dtype, scale=_chk(scale, torch.float32), rows_per_sample=rows_per_sample)
+
+    @staticmethod
+    def backward(ctx, g):
+        (scale,) = ctx.saved_tensors
+        rps, xdt = ctx.cfg
+        return map_copy(g, xdt, scale=scale, rows_per_sample=rps), None, None
+
+
+def draw_channel_scale(B, Cc, p, device, keep=None):
+    """-> (scale float32 [B, C] in {0, 1/(1-p)}, keep mask uint8 [B*C]) of one Dropout2d call. The mask is `keep` when given, else
+    drawn by evp_dropout_fwd from a key drawn on the device (draw_drop_seed): a replayed graph draws a new one."""
+    ones = torch.ones(B * Cc, dtype=torch.float32, device=device)
+    rd = BlockDrop(drop=p, seed=0 if keep is not None else draw_drop_seed(device),
+                   masks=None if keep is None else {"c": keep.to(device=device, dtype=torch.uint8).contiguous().view(-1)})
+    scale, mask = dropout_fwd(ones, rd, "c")
+    return scale.view(B, Cc), mask
+
+
+class DenseClsFn(torch.autograd.Function):
+    """The heads' `conv_dense` (nn.Conv2d(channels, out_channels, 1); ft_dense_decoder.py:41,48) on a map -> float32 [B*H*W, out_channels].
+    11 classes or 2 flow components run zero-padded to 8 columns, as LinearFn's narrow heads do; the bias gradient is an ordered sum."""
+
+    @staticmethod
+    def forward(ctx, x, w, b):
+        T = _compute_dtype
+        xl = _contig(x.detach(), T)
+        R, K = xl.shape
+        N = w.shape[0]
+        Np = _pad8(N)
+        wl = lp_weight(w).view(N, K)
+        bias = b
+        if Np != N:
+            wp = torch.zeros(Np, K, dtype=wl.dtype, device=wl.device)
+            wp[:N].copy_(wl)
+            wl = wp
+            if b is not None:
+                bias = torch.zeros(Np, dtype=torch.float32, device=wl.device)
+                bias[:N].copy_(b.detach())
+        y = torch.empty(R, Np, dtype=torch.float32, device=x.device)
+        gemm(xl, wl, y, M=R, N=Np, K=K, bias=bias)
+        ctx.save_for_backward(xl, wl)
+        ctx.cfg = (N, x.dtype, x.requires_grad, tuple(w.shape))
+        return y[:, :N]
+
+    @staticmethod
+    def backward(ctx, g):
+        xl, wl = ctx.saved_tensors
+        N, xdt, need_dx, wshape = ctx.cfg
+        (R, K), Np = xl.shape, wl.shape[0]
+        if Np != N:
+            gp = torch.zeros(R, Np, dtype=torch.float32, device=g.device)
+            map_copy(g, torch.float32, (gp, 0))
+        else:
+            gp = _contig(g, torch.float32)
+        gl = cast(gp, xl.dtype)
+        dw = db = dx = None
+        if ctx.needs_input_grad[1]:
+            dw = _wgrad(gl, xl, Np, K, R)[:N].contiguous().view(wshape)
+        if ctx.needs_input_grad[2]:
+            db = colsum_ordered(gp)[:N].contiguous()
+        if need_dx:
+            dx = torch.empty(R, K, dtype=xdt, device=g.device)
+            gemm(gl, wl, dx, M=R, N=K, K=Np, trans_b=True, ldb=K)
+        return dx, dw, db

@@ -608,6 +608,46 @@ int evp_rows_scale_f32(const float *x, const float *u, float keep_prob, const fl
 int evp_dropout_fwd(const void *x, int dtype, void *out, void *mask, int64_t n, float p, uint64_t seed, const void *seed_dev, uint64_t offset, void *stream);
 int evp_dropout_apply(const void *x, int dtype, const void *mask, void *out, int64_t n, float scale, void *stream);
 
+/* ------------------------------------------------------------------------------------------------ K26 dense-prediction heads
+ * What the UPerNet / FCN decoders (model/finetune_dense/ft_dense_decoder.py) need besides evp_gemm and evp_batchnorm_*. Every map is
+ * token-major: row (b, y, x) = (b * H + y) * W + x of a [B*H*W, C] matrix with a leading dimension in elements, so a channel slice of a
+ * wider buffer is a map; outputs take a leading dimension and a column offset (torch.cat(dim=1) = each producer writes its slice).
+ * Element types EVP_F32 | EVP_BF16 per operand, float32 arithmetic. No atomics: adjoints are gathers and every sum has a fixed order.
+ *   evp_im2col3x3   cols[(b,y,x), c*9 + ky*3 + kx] = in[b, y+ky-1, x+kx-1, c] or 0 outside the map: the patch rows of nn.Conv2d(3, stride 1,
+ *                   padding 1), inner order = conv.weight.view(O, I*9), so conv = evp_gemm(cols, weight). C % 8 == 0, ldc % 8 == 0, cols
+ *                   16-byte aligned, W <= 510.
+ *   evp_col2im3x3   its adjoint: dx[b,y,x,c] = sum_{ky,kx} dcols[(b, y-ky+1, x-kx+1), c*9 + ky*3 + kx] (ky outer).
+ *   evp_adaptive_avgpool_fwd / _bwd   nn.AdaptiveAvgPool2d(s): bin i covers [floor(i n / s), ceil((i+1) n / s)) per axis (bins overlap when
+ *                   s does not divide n); out [B*s*s, C]. Backward: dx[b,y,x,c] = sum over the bins containing (y,x) of g / bin area.
+ *   evp_upsample_bilinear_fwd / _bwd  F.interpolate(mode="bilinear", align_corners=False) from h x w to H x W (ATen's arithmetic, see
+ *                   evp_view_augment_bilinear_f32; h = w = 1 gives a constant map). Backward: g [B*H*W, C] -> dx [B*h*w, C].
+ *   evp_channel_scale   out[(b,p), c] = in[(b,p), c] * m[b, c] for p < P: nn.Dropout2d with m in {0, 1/(1-p)} float32 [B, C] (drawn by
+ *                   evp_dropout_fwd on a table of ones), forward and backward alike, and the cast of its output; m == NULL: a strided
+ *                   cast-copy.
+ *   evp_batchnorm_eval  y = (x - running_mean) / sqrt(running_var + eps) * gamma + beta, relu != 0: max(., 0). gamma/beta may be NULL.
+ *   evp_colsum_ordered  out[c] = sum_r x[r, c] in an order that depends on nothing but R (the bias gradient of a convolution). */
+int evp_im2col3x3(const void *in, int in_dtype, int64_t ldi, int B, int H, int W, int C, void *cols, int cols_dtype, int64_t ldc, void *stream);
+int evp_col2im3x3(const void *dcols, int dtype, int64_t ldc, int B, int H, int W, int C, void *dx, int dx_dtype, int64_t ldx, int64_t xoff,
+                  void *stream);
+int evp_adaptive_avgpool_fwd(const void *in, int in_dtype, int64_t ldi, int B, int H, int W, int C, int s, void *out, int out_dtype,
+                             int64_t ldo, int64_t ooff, void *stream);
+int evp_adaptive_avgpool_bwd(const void *g, int g_dtype, int64_t ldg, int B, int H, int W, int C, int s, void *dx, int dx_dtype,
+                             int64_t ldx, int64_t xoff, void *stream);
+int evp_upsample_bilinear_fwd(const void *in, int in_dtype, int64_t ldi, int B, int h, int w, int H, int W, int C, void *out,
+                              int out_dtype, int64_t ldo, int64_t ooff, void *stream);
+int evp_upsample_bilinear_bwd(const void *g, int g_dtype, int64_t ldg, int B, int h, int w, int H, int W, int C, void *dx, int dx_dtype,
+                              int64_t ldx, int64_t xoff, void *stream);
+int evp_channel_scale(const void *in, int in_dtype, int64_t ldi, const float *m, int B, int P, int C, void *out, int out_dtype, int64_t ldo,
+                      int64_t ooff, void *stream);
+int evp_batchnorm_eval(const void *x, int x_dtype, int64_t ldx, int64_t R, int C, const float *gamma, const float *beta,
+                       const float *running_mean, const float *running_var, float eps, int relu, void *y, int y_dtype, int64_t ldo,
+                       int64_t ooff, void *stream);
+/* data gradient of evp_batchnorm_eval: dx = g * gamma / sqrt(running_var + eps), zero where relu != 0 and the saved output y <= 0 */
+int evp_batchnorm_eval_bwd(const void *g, int g_dtype, int64_t ldg, const void *y, int y_dtype, int64_t ldy, int64_t R, int C,
+                           const float *gamma, const float *running_var, float eps, int relu, void *dx, int dx_dtype, int64_t ldx,
+                           void *stream);
+int evp_colsum_ordered(const void *x, int dtype, int64_t R, int C, int64_t ld, float *out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
