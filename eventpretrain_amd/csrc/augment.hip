@@ -43,9 +43,8 @@ extern "C" int evp_view_augment_f32(const float *in, const int32_t *params, floa
 // ---- the fine-tuning recipe's view: crop -> BILINEAR resize -> horizontal flip -> time flip ------------------------------
 // evg_augment(mode=args.resize_mode) with the fine-tuning default --resize_mode bilinear (dataset/finetune_cls/
 // ft_n_imagenet_dataset.py:104-106, main_finetune_cls.py:48). F.interpolate(mode='bilinear', align_corners=None) on the cropped view
-// = ATen upsample_bilinear2d, restated in float32 so that the result is EQUAL to the CPU op's, not close to it: per axis
-//   src = max(0, fmaf(in / out, dst + 0.5, -0.5))   one fused multiply-add (an unfused coordinate moves results by up to 1.2e-4)
-//   i0 = min((int)src, in - 1), i1 = i0 + (i0 < in - 1): clamped at the CROP's edge;  l1 = src - i0, l0 = 1 - l1
+// = ATen upsample_bilinear2d, restated in float32 so that the result is EQUAL to the CPU op's, not close to it: per axis the taps of
+// tap_of (evp_common.h) with n_in = the crop's extent, so they are clamped at the CROP's edge,
 // and over the two axes, rows first: top = fmaf(lx0, a, lx1 * b), bot = fmaf(lx0, c, lx1 * d), out = fmaf(ly0, top, ly1 * bot) -- the
 // other sum orders differ from ATen in 20-50 % of the elements by 1-2 ulp. (This is ATen's GENERIC float32 kernel, the one a 5 x 224 x
 // 224 view gets; for Hout + Wout <= 128 the CPU op switches to a channels-last vector kernel with pre-multiplied weights, 1 ulp apart.)
@@ -59,27 +58,19 @@ __global__ __launch_bounds__(256) void view_augment_bilinear_kernel(const float 
   const int32_t *pr = params + (int64_t)b * 6;
   const int x0 = pr[0], y0 = pr[1], w = pr[2], h = pr[3], hflip = pr[4], tflip = pr[5];
   const float sy = (float)h / (float)Hout, sx = (float)w / (float)Wout;
-  const float ry = fmaxf(0.0f, __builtin_fmaf(sy, (float)y + 0.5f, -0.5f));
-  int iy0 = (int)ry;
-  iy0 = iy0 < h - 1 ? iy0 : h - 1;
-  const int iy1 = iy0 + (iy0 < h - 1 ? 1 : 0);
-  const float ly1 = ry - (float)iy0, ly0 = 1.0f - ly1;
-  const int64_t r0 = (int64_t)(y0 + iy0) * Win, r1 = (int64_t)(y0 + iy1) * Win;
+  const Tap ty = tap_of(y, h, sy);
+  const int64_t r0 = (int64_t)(y0 + ty.i0) * Win, r1 = (int64_t)(y0 + ty.i1) * Win;
   const float sgn = (tflip && negate) ? -1.0f : 1.0f;
   for (int x = blockIdx.x * 256 + threadIdx.x; x < Wout; x += gridDim.x * 256) {
     const int xr = hflip ? Wout - 1 - x : x;          // the flip acts on the resized view
-    const float rx = fmaxf(0.0f, __builtin_fmaf(sx, (float)xr + 0.5f, -0.5f));
-    int ix0 = (int)rx;
-    ix0 = ix0 < w - 1 ? ix0 : w - 1;
-    const int ix1 = ix0 + (ix0 < w - 1 ? 1 : 0);
-    const float lx1 = rx - (float)ix0, lx0 = 1.0f - lx1;
-    const int xa = x0 + ix0, xb = x0 + ix1;
+    const Tap tx = tap_of(xr, w, sx);
+    const int xa = x0 + tx.i0, xb = x0 + tx.i1;
     for (int c = 0; c < C; ++c) {
       const int cs = tflip ? C - 1 - c : c;
       const float *src = in + ((int64_t)b * C + cs) * Hin * Win;
-      const float top = __builtin_fmaf(lx0, src[r0 + xa], lx1 * src[r0 + xb]);
-      const float bot = __builtin_fmaf(lx0, src[r1 + xa], lx1 * src[r1 + xb]);
-      out[(((int64_t)b * C + c) * Hout + y) * Wout + x] = sgn * __builtin_fmaf(ly0, top, ly1 * bot);
+      const float top = fmaf(tx.l0, src[r0 + xa], tx.l1 * src[r0 + xb]);
+      const float bot = fmaf(tx.l0, src[r1 + xa], tx.l1 * src[r1 + xb]);
+      out[(((int64_t)b * C + c) * Hout + y) * Wout + x] = sgn * fmaf(ty.l0, top, ty.l1 * bot);
     }
   }
 }

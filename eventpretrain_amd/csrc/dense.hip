@@ -60,172 +60,150 @@ __global__ __launch_bounds__(256) void im2col3x3_kernel(const void *__restrict__
   }
 }
 
-// dx[b,y,x,c] = sum over (ky, kx), ky outer, of dcols[(b, y-ky+1, x-kx+1), c*9 + ky*3 + kx] where that token exists: <= 9 terms, fixed order
-__global__ __launch_bounds__(256) void col2im3x3_kernel(const void *__restrict__ dcols, int dtype, int64_t ldc, int B, int H, int W, int C,
-                                                        void *__restrict__ dx, int dx_dtype, int64_t ldx, int64_t xoff) {
-  const int64_t total = (int64_t)B * H * W * C;
+// ---- the element kernels: one map form ------------------------------------------------------------------------------------------------
+// out[row, off + c] = op(row, c) over an [rows, C] map: the grid-stride loop, the (c, row) decode and the strided store, once. An Op
+// holds its operands and returns the float of one element; its sums keep their order (rows outer), so the result has one set of bits.
+template <typename Op>
+__global__ __launch_bounds__(256) void map_kernel(const Op op, int64_t rows, int C, void *__restrict__ out, int out_dtype, int64_t ldo, int64_t ooff) {
+  const int64_t total = rows * C;
   for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (int64_t)gridDim.x * 256) {
     const int c = (int)(e % C);
     const int64_t row = e / C;
-    const int x = (int)(row % W), y = (int)((row / W) % H);
+    st_any(out, out_dtype, row * ldo + ooff + c, op(row, c));
+  }
+}
+
+// row = (b * H + y) * W + x
+struct Pix { int b, y, x; };
+__device__ __forceinline__ Pix pix_of(int64_t row, int H, int W) {
+  return Pix{(int)(row / ((int64_t)H * W)), (int)((row / W) % H), (int)(row % W)};
+}
+
+// dx[b,y,x,c] = sum over (ky, kx), ky outer, of dcols[(b, y-ky+1, x-kx+1), c*9 + ky*3 + kx] where that token exists: <= 9 terms, fixed order
+struct Col2im3x3 {
+  const void *dcols; int dtype; int64_t ldc; int H, W;
+  __device__ float operator()(int64_t row, int c) const {
+    const Pix p = pix_of(row, H, W);
     float acc = 0.f;
 #pragma unroll
     for (int ky = 0; ky < 3; ++ky) {
-      const int yo = y - ky + 1;
+      const int yo = p.y - ky + 1;
       if (yo < 0 || yo >= H) continue;
 #pragma unroll
       for (int kx = 0; kx < 3; ++kx) {
-        const int xo = x - kx + 1;
+        const int xo = p.x - kx + 1;
         if (xo < 0 || xo >= W) continue;
-        acc += ld_any(dcols, dtype, (row + (int64_t)(yo - y) * W + (xo - x)) * ldc + (int64_t)c * 9 + ky * 3 + kx);
+        acc += ld_any(dcols, dtype, (row + (int64_t)(yo - p.y) * W + (xo - p.x)) * ldc + (int64_t)c * 9 + ky * 3 + kx);
       }
     }
-    st_any(dx, dx_dtype, row * ldx + xoff + c, acc);
+    return acc;
   }
-}
+};
 
 // ---- adaptive average pooling -------------------------------------------------------------------------------------------------------
 __device__ __forceinline__ int bin_lo(int i, int n, int s) { return (i * n) / s; }
 __device__ __forceinline__ int bin_hi(int i, int n, int s) { return ((i + 1) * n + s - 1) / s; }
 
-__global__ __launch_bounds__(256) void avgpool_fwd_kernel(const void *__restrict__ in, int in_dtype, int64_t ldi, int B, int H, int W, int C, int s,
-                                                          void *__restrict__ out, int out_dtype, int64_t ldo, int64_t ooff) {
-  const int64_t total = (int64_t)B * s * s * C;
-  for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (int64_t)gridDim.x * 256) {
-    const int c = (int)(e % C);
-    const int64_t row = e / C;
-    const int j = (int)(row % s), i = (int)((row / s) % s), b = (int)(row / ((int64_t)s * s));
-    const int y0 = bin_lo(i, H, s), y1 = bin_hi(i, H, s), x0 = bin_lo(j, W, s), x1 = bin_hi(j, W, s);
+struct AvgPoolFwd {      // row = (b, i, j) of the [B*s*s, C] output
+  const void *in; int in_dtype; int64_t ldi; int H, W, s;
+  __device__ float operator()(int64_t row, int c) const {
+    const Pix p = pix_of(row, s, s);
+    const int y0 = bin_lo(p.y, H, s), y1 = bin_hi(p.y, H, s), x0 = bin_lo(p.x, W, s), x1 = bin_hi(p.x, W, s);
     float acc = 0.f;
     for (int y = y0; y < y1; ++y)
-      for (int x = x0; x < x1; ++x) acc += ld_any(in, in_dtype, ((int64_t)(b * H + y) * W + x) * ldi + c);
-    st_any(out, out_dtype, row * ldo + ooff + c, acc / (float)((y1 - y0) * (x1 - x0)));
+      for (int x = x0; x < x1; ++x) acc += ld_any(in, in_dtype, ((int64_t)(p.b * H + y) * W + x) * ldi + c);
+    return acc / (float)((y1 - y0) * (x1 - x0));
   }
-}
+};
 
 // dx[b,y,x,c] = sum over the bins (i, j) that contain (y, x), i outer, of g[b,i,j,c] / area(i, j)
-__global__ __launch_bounds__(256) void avgpool_bwd_kernel(const void *__restrict__ g, int g_dtype, int64_t ldg, int B, int H, int W, int C, int s,
-                                                          void *__restrict__ dx, int dx_dtype, int64_t ldx, int64_t xoff) {
-  const int64_t total = (int64_t)B * H * W * C;
-  for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (int64_t)gridDim.x * 256) {
-    const int c = (int)(e % C);
-    const int64_t row = e / C;
-    const int x = (int)(row % W), y = (int)((row / W) % H), b = (int)(row / ((int64_t)H * W));
+struct AvgPoolBwd {
+  const void *g; int g_dtype; int64_t ldg; int H, W, s;
+  __device__ float operator()(int64_t row, int c) const {
+    const Pix p = pix_of(row, H, W);
     float acc = 0.f;
     for (int i = 0; i < s; ++i) {
       const int y0 = bin_lo(i, H, s), y1 = bin_hi(i, H, s);
-      if (y < y0 || y >= y1) continue;
+      if (p.y < y0 || p.y >= y1) continue;
       for (int j = 0; j < s; ++j) {
         const int x0 = bin_lo(j, W, s), x1 = bin_hi(j, W, s);
-        if (x < x0 || x >= x1) continue;
-        acc += ld_any(g, g_dtype, ((int64_t)(b * s + i) * s + j) * ldg + c) / (float)((y1 - y0) * (x1 - x0));
+        if (p.x < x0 || p.x >= x1) continue;
+        acc += ld_any(g, g_dtype, ((int64_t)(p.b * s + i) * s + j) * ldg + c) / (float)((y1 - y0) * (x1 - x0));
       }
     }
-    st_any(dx, dx_dtype, row * ldx + xoff + c, acc);
+    return acc;
   }
-}
+};
 
-// ---- bilinear resize ----------------------------------------------------------------------------------------------------------------
-// ATen upsample_bilinear2d, align_corners = False, per axis (as csrc/augment.hip restates it): src = max(0, fmaf(in / out, dst + 0.5, -0.5)),
-// i0 = min((int)src, in - 1), i1 = i0 + (i0 < in - 1), l1 = src - i0, l0 = 1 - l1.
-struct Tap { int i0, i1; float l0, l1; };
-__device__ __forceinline__ Tap tap_of(int d, int n_in, float scale) {
-  const float src = fmaxf(0.f, fmaf(scale, (float)d + 0.5f, -0.5f));
-  Tap t;
-  t.i0 = min((int)src, n_in - 1);
-  t.i1 = t.i0 + (t.i0 < n_in - 1 ? 1 : 0);
-  t.l1 = src - (float)t.i0;
-  t.l0 = 1.f - t.l1;
-  return t;
-}
-
-__global__ __launch_bounds__(256) void upsample_fwd_kernel(const void *__restrict__ in, int in_dtype, int64_t ldi, int B, int h, int w, int H, int W,
-                                                           int C, void *__restrict__ out, int out_dtype, int64_t ldo, int64_t ooff) {
-  const float sy = (float)h / (float)H, sx = (float)w / (float)W;
-  const int64_t total = (int64_t)B * H * W * C;
-  for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (int64_t)gridDim.x * 256) {
-    const int c = (int)(e % C);
-    const int64_t row = e / C;
-    const int x = (int)(row % W), y = (int)((row / W) % H), b = (int)(row / ((int64_t)H * W));
-    const Tap ty = tap_of(y, h, sy), tx = tap_of(x, w, sx);
-    const int64_t r0 = (int64_t)(b * h + ty.i0) * w, r1 = (int64_t)(b * h + ty.i1) * w;
+// ---- bilinear resize (Tap / tap_of: evp_common.h) ---------------------------------------------------------------------------------------
+struct UpsampleFwd {      // [B*h*w, C] -> row (b, y, x) of [B*H*W, C]
+  const void *in; int in_dtype; int64_t ldi; int h, w, H, W;
+  __device__ float operator()(int64_t row, int c) const {
+    const float sy = (float)h / (float)H, sx = (float)w / (float)W;
+    const Pix p = pix_of(row, H, W);
+    const Tap ty = tap_of(p.y, h, sy), tx = tap_of(p.x, w, sx);
+    const int64_t r0 = (int64_t)(p.b * h + ty.i0) * w, r1 = (int64_t)(p.b * h + ty.i1) * w;
     const float a = ld_any(in, in_dtype, (r0 + tx.i0) * ldi + c), bb = ld_any(in, in_dtype, (r0 + tx.i1) * ldi + c);
     const float cc = ld_any(in, in_dtype, (r1 + tx.i0) * ldi + c), d = ld_any(in, in_dtype, (r1 + tx.i1) * ldi + c);
     const float top = fmaf(tx.l0, a, tx.l1 * bb), bot = fmaf(tx.l0, cc, tx.l1 * d);
-    st_any(out, out_dtype, row * ldo + ooff + c, fmaf(ty.l0, top, ty.l1 * bot));
+    return fmaf(ty.l0, top, ty.l1 * bot);
   }
-}
+};
 
 // gather form of the adjoint: source pixel (ys, xs) sums, rows outer, over the destination pixels one of whose taps is (ys, xs)
-__global__ __launch_bounds__(256) void upsample_bwd_kernel(const void *__restrict__ g, int g_dtype, int64_t ldg, int B, int h, int w, int H, int W,
-                                                           int C, void *__restrict__ dx, int dx_dtype, int64_t ldx, int64_t xoff) {
-  const float sy = (float)h / (float)H, sx = (float)w / (float)W;
-  const int64_t total = (int64_t)B * h * w * C;
-  for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (int64_t)gridDim.x * 256) {
-    const int c = (int)(e % C);
-    const int64_t row = e / C;
-    const int xs = (int)(row % w), ys = (int)((row / w) % h), b = (int)(row / ((int64_t)h * w));
+struct UpsampleBwd {
+  const void *g; int g_dtype; int64_t ldg; int h, w, H, W;
+  __device__ float operator()(int64_t row, int c) const {
+    const float sy = (float)h / (float)H, sx = (float)w / (float)W;
+    const Pix p = pix_of(row, h, w);      // the source pixel
     float acc = 0.f;
     for (int y = 0; y < H; ++y) {
       const Tap ty = tap_of(y, h, sy);
-      const float wy = (ty.i0 == ys ? ty.l0 : 0.f) + (ty.i1 == ys ? ty.l1 : 0.f);
-      if (ty.i0 != ys && ty.i1 != ys) continue;
+      const float wy = (ty.i0 == p.y ? ty.l0 : 0.f) + (ty.i1 == p.y ? ty.l1 : 0.f);
+      if (ty.i0 != p.y && ty.i1 != p.y) continue;
       for (int x = 0; x < W; ++x) {
         const Tap tx = tap_of(x, w, sx);
-        if (tx.i0 != xs && tx.i1 != xs) continue;
-        const float wx = (tx.i0 == xs ? tx.l0 : 0.f) + (tx.i1 == xs ? tx.l1 : 0.f);
-        acc += wy * wx * ld_any(g, g_dtype, ((int64_t)(b * H + y) * W + x) * ldg + c);
+        if (tx.i0 != p.x && tx.i1 != p.x) continue;
+        const float wx = (tx.i0 == p.x ? tx.l0 : 0.f) + (tx.i1 == p.x ? tx.l1 : 0.f);
+        acc += wy * wx * ld_any(g, g_dtype, ((int64_t)(p.b * H + y) * W + x) * ldg + c);
       }
     }
-    st_any(dx, dx_dtype, row * ldx + xoff + c, acc);
+    return acc;
   }
-}
+};
 
 // ---- channel scale / strided cast-copy ----------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void channel_scale_kernel(const void *__restrict__ in, int in_dtype, int64_t ldi, const float *__restrict__ m, int B,
-                                                            int P, int C, void *__restrict__ out, int out_dtype, int64_t ldo, int64_t ooff) {
-  const int64_t total = (int64_t)B * P * C;
-  for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (int64_t)gridDim.x * 256) {
-    const int c = (int)(e % C);
-    const int64_t row = e / C;
+struct ChannelScale {
+  const void *in; int in_dtype; int64_t ldi; const float *m; int P, C;
+  __device__ float operator()(int64_t row, int c) const {
     float v = ld_any(in, in_dtype, row * ldi + c);
     if (m) v *= m[(row / P) * C + c];
-    st_any(out, out_dtype, row * ldo + ooff + c, v);
+    return v;
   }
-}
+};
 
 // ---- BatchNorm on running statistics ------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void batchnorm_eval_kernel(const void *__restrict__ x, int x_dtype, int64_t ldx, int64_t R, int C,
-                                                             const float *__restrict__ gamma, const float *__restrict__ beta,
-                                                             const float *__restrict__ rmean, const float *__restrict__ rvar, float eps, int relu,
-                                                             void *__restrict__ y, int y_dtype, int64_t ldo, int64_t ooff) {
-  const int64_t total = R * C;
-  for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (int64_t)gridDim.x * 256) {
-    const int c = (int)(e % C);
-    const int64_t row = e / C;
+struct BatchNormEval {
+  const void *x; int x_dtype; int64_t ldx; const float *gamma, *beta, *rmean, *rvar; float eps; int relu;
+  __device__ float operator()(int64_t row, int c) const {
     const float invstd = 1.f / sqrtf(rvar[c] + eps);
     float v = (ld_any(x, x_dtype, row * ldx + c) - rmean[c]) * invstd;
     if (gamma) v = v * gamma[c] + beta[c];
     if (relu) v = fmaxf(v, 0.f);
-    st_any(y, y_dtype, row * ldo + ooff + c, v);
+    return v;
   }
-}
+};
 
 // data gradient of the above: dx = g * gamma / sqrt(running_var + eps), zero where the ReLU output y is not positive
-__global__ __launch_bounds__(256) void batchnorm_eval_bwd_kernel(const void *__restrict__ g, int g_dtype, int64_t ldg, const void *__restrict__ y,
-                                                                 int y_dtype, int64_t ldy, int64_t R, int C, const float *__restrict__ gamma,
-                                                                 const float *__restrict__ rvar, float eps, int relu, void *__restrict__ dx,
-                                                                 int dx_dtype, int64_t ldx) {
-  const int64_t total = R * C;
-  for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (int64_t)gridDim.x * 256) {
-    const int c = (int)(e % C);
-    const int64_t row = e / C;
+struct BatchNormEvalBwd {
+  const void *g; int g_dtype; int64_t ldg; const void *y; int y_dtype; int64_t ldy; const float *gamma, *rvar; float eps; int relu;
+  __device__ float operator()(int64_t row, int c) const {
     float v = ld_any(g, g_dtype, row * ldg + c) * (1.f / sqrtf(rvar[c] + eps));
     if (gamma) v *= gamma[c];
     if (relu && !(ld_any(y, y_dtype, row * ldy + c) > 0.f)) v = 0.f;
-    st_any(dx, dx_dtype, row * ldx + c, v);
+    return v;
   }
-}
+};
 
 // ---- ordered column sums ------------------------------------------------------------------------------------------------------------
 // out[c] = sum_r x[r, c]: 64 columns per workgroup, 4 row lanes per column (rows r = lane, lane + 4, ...), the four partials added in
@@ -239,6 +217,19 @@ __global__ __launch_bounds__(256) void colsum_ordered_kernel(const void *__restr
   part[lane][cl] = acc;
   __syncthreads();
   if (lane == 0 && c < C) out[c] = ((part[0][cl] + part[1][cl]) + part[2][cl]) + part[3][cl];
+}
+
+// The host side of a map entry point, once: `in` is the map the Op reads first (its rows are in_width elements wide, ldi apart), the
+// output is the slice [rows, ooff : ooff + C] of rows ldo apart. `dims_ok`: the entry point's own shape rules.
+template <typename Op>
+int map_launch(const char *name, const Op &op, const void *in, int in_dtype, int64_t ldi, int64_t in_width, bool dims_ok, int64_t rows, int C,
+               void *out, int out_dtype, int64_t ldo, int64_t ooff, void *stream) {
+  EVP_CHECK_ARG(in && out, EVP_EINVAL, "%s: null pointer", name);
+  EVP_CHECK_ARG(dtype_ok(in_dtype) && dtype_ok(out_dtype), EVP_EINVAL, "%s: bad dtype", name);
+  EVP_CHECK_ARG(dims_ok && ldi >= in_width && ooff >= 0 && ldo >= ooff + C, EVP_ESHAPE, "%s: bad shape", name);
+  hipLaunchKernelGGL(map_kernel<Op>, dim3(grid_for(rows * C)), dim3(256), 0, (hipStream_t)stream, op, rows, C, out, out_dtype, ldo, ooff);
+  EVP_CHECK_LAUNCH(name);
+  return EVP_OK;
 }
 
 }  // namespace
@@ -267,91 +258,56 @@ extern "C" int evp_im2col3x3(const void *in, int in_dtype, int64_t ldi, int B, i
 
 extern "C" int evp_col2im3x3(const void *dcols, int dtype, int64_t ldc, int B, int H, int W, int C, void *dx, int dx_dtype, int64_t ldx, int64_t xoff,
                              void *stream) {
-  EVP_CHECK_ARG(dcols && dx, EVP_EINVAL, "evp_col2im3x3: null pointer");
-  EVP_CHECK_ARG(dtype_ok(dtype) && dtype_ok(dx_dtype), EVP_EINVAL, "evp_col2im3x3: bad dtype");
-  EVP_CHECK_ARG(DENSE_MAP_ARGS_OK(B, H, W, C) && ldc >= (int64_t)C * 9 && xoff >= 0 && ldx >= xoff + C, EVP_ESHAPE, "evp_col2im3x3: bad shape");
-  hipLaunchKernelGGL(col2im3x3_kernel, dim3(grid_for((int64_t)B * H * W * C)), dim3(256), 0, (hipStream_t)stream, dcols, dtype, ldc, B, H, W, C, dx,
-                     dx_dtype, ldx, xoff);
-  EVP_CHECK_LAUNCH("evp_col2im3x3");
-  return EVP_OK;
+  return map_launch("evp_col2im3x3", Col2im3x3{dcols, dtype, ldc, H, W}, dcols, dtype, ldc, (int64_t)C * 9, DENSE_MAP_ARGS_OK(B, H, W, C),
+                    (int64_t)B * H * W, C, dx, dx_dtype, ldx, xoff, stream);
 }
 
 extern "C" int evp_adaptive_avgpool_fwd(const void *in, int in_dtype, int64_t ldi, int B, int H, int W, int C, int s, void *out, int out_dtype,
                                         int64_t ldo, int64_t ooff, void *stream) {
-  EVP_CHECK_ARG(in && out && dtype_ok(in_dtype) && dtype_ok(out_dtype), EVP_EINVAL, "evp_adaptive_avgpool_fwd: bad argument");
-  EVP_CHECK_ARG(DENSE_MAP_ARGS_OK(B, H, W, C) && s > 0 && s <= 4096 && ldi >= C && ooff >= 0 && ldo >= ooff + C, EVP_ESHAPE,
-                "evp_adaptive_avgpool_fwd: bad shape");
-  hipLaunchKernelGGL(avgpool_fwd_kernel, dim3(grid_for((int64_t)B * s * s * C)), dim3(256), 0, (hipStream_t)stream, in, in_dtype, ldi, B, H, W, C, s,
-                     out, out_dtype, ldo, ooff);
-  EVP_CHECK_LAUNCH("evp_adaptive_avgpool_fwd");
-  return EVP_OK;
+  return map_launch("evp_adaptive_avgpool_fwd", AvgPoolFwd{in, in_dtype, ldi, H, W, s}, in, in_dtype, ldi, C,
+                    DENSE_MAP_ARGS_OK(B, H, W, C) && s > 0 && s <= 4096, (int64_t)B * s * s, C, out, out_dtype, ldo, ooff, stream);
 }
 
 extern "C" int evp_adaptive_avgpool_bwd(const void *g, int g_dtype, int64_t ldg, int B, int H, int W, int C, int s, void *dx, int dx_dtype,
                                         int64_t ldx, int64_t xoff, void *stream) {
-  EVP_CHECK_ARG(g && dx && dtype_ok(g_dtype) && dtype_ok(dx_dtype), EVP_EINVAL, "evp_adaptive_avgpool_bwd: bad argument");
-  EVP_CHECK_ARG(DENSE_MAP_ARGS_OK(B, H, W, C) && s > 0 && s <= 4096 && ldg >= C && xoff >= 0 && ldx >= xoff + C, EVP_ESHAPE,
-                "evp_adaptive_avgpool_bwd: bad shape");
-  hipLaunchKernelGGL(avgpool_bwd_kernel, dim3(grid_for((int64_t)B * H * W * C)), dim3(256), 0, (hipStream_t)stream, g, g_dtype, ldg, B, H, W, C, s, dx,
-                     dx_dtype, ldx, xoff);
-  EVP_CHECK_LAUNCH("evp_adaptive_avgpool_bwd");
-  return EVP_OK;
+  return map_launch("evp_adaptive_avgpool_bwd", AvgPoolBwd{g, g_dtype, ldg, H, W, s}, g, g_dtype, ldg, C,
+                    DENSE_MAP_ARGS_OK(B, H, W, C) && s > 0 && s <= 4096, (int64_t)B * H * W, C, dx, dx_dtype, ldx, xoff, stream);
 }
 
 extern "C" int evp_upsample_bilinear_fwd(const void *in, int in_dtype, int64_t ldi, int B, int h, int w, int H, int W, int C, void *out,
                                          int out_dtype, int64_t ldo, int64_t ooff, void *stream) {
-  EVP_CHECK_ARG(in && out && dtype_ok(in_dtype) && dtype_ok(out_dtype), EVP_EINVAL, "evp_upsample_bilinear_fwd: bad argument");
-  EVP_CHECK_ARG(DENSE_MAP_ARGS_OK(B, H, W, C) && DENSE_MAP_ARGS_OK(B, h, w, C) && ldi >= C && ooff >= 0 && ldo >= ooff + C, EVP_ESHAPE,
-                "evp_upsample_bilinear_fwd: bad shape");
-  hipLaunchKernelGGL(upsample_fwd_kernel, dim3(grid_for((int64_t)B * H * W * C)), dim3(256), 0, (hipStream_t)stream, in, in_dtype, ldi, B, h, w, H, W,
-                     C, out, out_dtype, ldo, ooff);
-  EVP_CHECK_LAUNCH("evp_upsample_bilinear_fwd");
-  return EVP_OK;
+  return map_launch("evp_upsample_bilinear_fwd", UpsampleFwd{in, in_dtype, ldi, h, w, H, W}, in, in_dtype, ldi, C,
+                    DENSE_MAP_ARGS_OK(B, H, W, C) && DENSE_MAP_ARGS_OK(B, h, w, C), (int64_t)B * H * W, C, out, out_dtype, ldo, ooff, stream);
 }
 
 extern "C" int evp_upsample_bilinear_bwd(const void *g, int g_dtype, int64_t ldg, int B, int h, int w, int H, int W, int C, void *dx, int dx_dtype,
                                          int64_t ldx, int64_t xoff, void *stream) {
-  EVP_CHECK_ARG(g && dx && dtype_ok(g_dtype) && dtype_ok(dx_dtype), EVP_EINVAL, "evp_upsample_bilinear_bwd: bad argument");
-  EVP_CHECK_ARG(DENSE_MAP_ARGS_OK(B, H, W, C) && DENSE_MAP_ARGS_OK(B, h, w, C) && ldg >= C && xoff >= 0 && ldx >= xoff + C, EVP_ESHAPE,
-                "evp_upsample_bilinear_bwd: bad shape");
-  hipLaunchKernelGGL(upsample_bwd_kernel, dim3(grid_for((int64_t)B * h * w * C)), dim3(256), 0, (hipStream_t)stream, g, g_dtype, ldg, B, h, w, H, W, C,
-                     dx, dx_dtype, ldx, xoff);
-  EVP_CHECK_LAUNCH("evp_upsample_bilinear_bwd");
-  return EVP_OK;
+  return map_launch("evp_upsample_bilinear_bwd", UpsampleBwd{g, g_dtype, ldg, h, w, H, W}, g, g_dtype, ldg, C,
+                    DENSE_MAP_ARGS_OK(B, H, W, C) && DENSE_MAP_ARGS_OK(B, h, w, C), (int64_t)B * h * w, C, dx, dx_dtype, ldx, xoff, stream);
 }
 
 extern "C" int evp_channel_scale(const void *in, int in_dtype, int64_t ldi, const float *m, int B, int P, int C, void *out, int out_dtype, int64_t ldo,
                                  int64_t ooff, void *stream) {
-  EVP_CHECK_ARG(in && out && dtype_ok(in_dtype) && dtype_ok(out_dtype), EVP_EINVAL, "evp_channel_scale: bad argument");
-  EVP_CHECK_ARG(DENSE_MAP_ARGS_OK(B, P, 1, C) && ldi >= C && ooff >= 0 && ldo >= ooff + C, EVP_ESHAPE, "evp_channel_scale: bad shape");
-  hipLaunchKernelGGL(channel_scale_kernel, dim3(grid_for((int64_t)B * P * C)), dim3(256), 0, (hipStream_t)stream, in, in_dtype, ldi, m, B, P, C, out,
-                     out_dtype, ldo, ooff);
-  EVP_CHECK_LAUNCH("evp_channel_scale");
-  return EVP_OK;
+  return map_launch("evp_channel_scale", ChannelScale{in, in_dtype, ldi, m, P, C}, in, in_dtype, ldi, C, DENSE_MAP_ARGS_OK(B, P, 1, C),
+                    (int64_t)B * P, C, out, out_dtype, ldo, ooff, stream);
 }
 
 extern "C" int evp_batchnorm_eval(const void *x, int x_dtype, int64_t ldx, int64_t R, int C, const float *gamma, const float *beta,
                                   const float *running_mean, const float *running_var, float eps, int relu, void *y, int y_dtype, int64_t ldo,
                                   int64_t ooff, void *stream) {
-  EVP_CHECK_ARG(x && y && running_mean && running_var && dtype_ok(x_dtype) && dtype_ok(y_dtype), EVP_EINVAL, "evp_batchnorm_eval: bad argument");
+  EVP_CHECK_ARG(running_mean && running_var, EVP_EINVAL, "evp_batchnorm_eval: null pointer");
   EVP_CHECK_ARG((gamma == nullptr) == (beta == nullptr), EVP_EINVAL, "evp_batchnorm_eval: gamma and beta go together");
-  EVP_CHECK_ARG(R > 0 && R < (1ll << 31) && C > 0 && ldx >= C && ooff >= 0 && ldo >= ooff + C, EVP_ESHAPE, "evp_batchnorm_eval: bad shape");
-  hipLaunchKernelGGL(batchnorm_eval_kernel, dim3(grid_for(R * C)), dim3(256), 0, (hipStream_t)stream, x, x_dtype, ldx, R, C, gamma, beta, running_mean,
-                     running_var, eps, relu, y, y_dtype, ldo, ooff);
-  EVP_CHECK_LAUNCH("evp_batchnorm_eval");
-  return EVP_OK;
+  return map_launch("evp_batchnorm_eval", BatchNormEval{x, x_dtype, ldx, gamma, beta, running_mean, running_var, eps, relu}, x, x_dtype, ldx, C,
+                    DENSE_MAP_ARGS_OK(R, 1, 1, C), R, C, y, y_dtype, ldo, ooff, stream);
 }
 
 extern "C" int evp_batchnorm_eval_bwd(const void *g, int g_dtype, int64_t ldg, const void *y, int y_dtype, int64_t ldy, int64_t R, int C,
                                       const float *gamma, const float *running_var, float eps, int relu, void *dx, int dx_dtype, int64_t ldx,
                                       void *stream) {
-  EVP_CHECK_ARG(g && dx && running_var && dtype_ok(g_dtype) && dtype_ok(dx_dtype), EVP_EINVAL, "evp_batchnorm_eval_bwd: bad argument");
+  EVP_CHECK_ARG(running_var, EVP_EINVAL, "evp_batchnorm_eval_bwd: null pointer");
   EVP_CHECK_ARG(!relu || (y && dtype_ok(y_dtype) && ldy >= C), EVP_EINVAL, "evp_batchnorm_eval_bwd: relu needs y");
-  EVP_CHECK_ARG(R > 0 && R < (1ll << 31) && C > 0 && ldg >= C && ldx >= C, EVP_ESHAPE, "evp_batchnorm_eval_bwd: bad shape");
-  hipLaunchKernelGGL(batchnorm_eval_bwd_kernel, dim3(grid_for(R * C)), dim3(256), 0, (hipStream_t)stream, g, g_dtype, ldg, y, y_dtype, ldy, R, C,
-                     gamma, running_var, eps, relu, dx, dx_dtype, ldx);
-  EVP_CHECK_LAUNCH("evp_batchnorm_eval_bwd");
-  return EVP_OK;
+  return map_launch("evp_batchnorm_eval_bwd", BatchNormEvalBwd{g, g_dtype, ldg, y, y_dtype, ldy, gamma, running_var, eps, relu}, g, g_dtype, ldg, C,
+                    DENSE_MAP_ARGS_OK(R, 1, 1, C), R, C, dx, dx_dtype, ldx, 0, stream);
 }
 
 extern "C" int evp_colsum_ordered(const void *x, int dtype, int64_t R, int C, int64_t ld, float *out, void *stream) {

@@ -102,6 +102,23 @@ __device__ __forceinline__ float dgelu_f(float x) {
   return cdf + x * pdf;
 }
 
+// ---- one axis of a bilinear resize ------------------------------------------------------------------------------------------
+// ATen upsample_bilinear2d, align_corners = False, in float32 so that a result is EQUAL to the CPU op's: destination index d of n_out
+// reads source indices i0, i1 of n_in with weights l0, l1, scale = (float)n_in / (float)n_out:
+//   src = max(0, fmaf(scale, d + 0.5, -0.5))   one fused multiply-add (an unfused coordinate moves results by up to 1.2e-4)
+//   i0 = min((int)src, n_in - 1), i1 = i0 + (i0 < n_in - 1): clamped at the edge of the n_in source pixels;  l1 = src - i0, l0 = 1 - l1
+// (csrc/dense.hip: the map resize and its adjoint; csrc/augment.hip: the fine-tuning view, where n_in is the crop's extent).
+struct Tap { int i0, i1; float l0, l1; };
+__device__ __forceinline__ Tap tap_of(int d, int n_in, float scale) {
+  const float src = fmaxf(0.f, fmaf(scale, (float)d + 0.5f, -0.5f));
+  Tap t;
+  t.i0 = min((int)src, n_in - 1);
+  t.i1 = t.i0 + (t.i0 < n_in - 1 ? 1 : 0);
+  t.l1 = src - (float)t.i0;
+  t.l0 = 1.f - t.l1;
+  return t;
+}
+
 static inline int64_t ceil_div64(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
 // ---- zero fill as a KERNEL ------------------------------------------------------------------------------------------------

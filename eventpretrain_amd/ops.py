@@ -1010,6 +1010,47 @@ class LayerNormFn(torch.autograd.Function):
         return dx, (dx if ctx.has[0] else None), (dx if ctx.has[1] else None), dgamma, dbeta, None
 
 
+def _head_fwd(xl, wl, b):
+    """y = xl @ wl^T + b as float32 [M, _pad8(N)] for a weight [N, K] in xl's dtype: a width that is not a multiple of 8 runs with
+    zero rows behind the weight and zeros behind the bias. -> (y, the weight as it ran); the caller cuts y[:, :N]."""
+    M, K = xl.shape
+    N = wl.shape[0]
+    Np = _pad8(N)
+    bias = b
+    if Np != N:
+        wp = torch.zeros(Np, K, dtype=wl.dtype, device=wl.device)
+        wp[:N].copy_(wl)
+        wl = wp
+        if b is not None:
+            bias = torch.zeros(Np, dtype=torch.float32, device=wl.device)
+            bias[:N].copy_(b.detach())
+    y = torch.empty(M, Np, dtype=torch.float32, device=xl.device)
+    gemm(xl, wl, y, M=M, N=Np, K=K, bias=bias)
+    return y, wl
+
+
+def _head_bwd(g, xl, wl, N, pad_into, bias_sum, wparam, need_w, need_b, dx_dtype):
+    """Backward of _head_fwd on what it saved. g: the [M, N] gradient; where the head ran padded, `pad_into(gp)` copies it into the
+    zeroed float32 [M, _pad8(N)] buffer (the caller's copy kernel) and dw, db are cut back to N. `bias_sum(gp)`: the caller's column
+    sum; `wparam`: the parameter _wgrad may queue dw on (whole-width heads only), or None. -> (dx [M, K] in dx_dtype or None without
+    one, dw, db)."""
+    (M, K), Np = xl.shape, wl.shape[0]
+    if Np != N:
+        gp = torch.zeros(M, Np, dtype=torch.float32, device=g.device)
+        pad_into(gp)
+    else:
+        gp = _contig(g, torch.float32)
+    gl = cast(gp, xl.dtype)
+    cut = (lambda t: t[:N].contiguous()) if Np != N else (lambda t: t)
+    dw = cut(_wgrad(gl, xl, Np, K, M, wparam)) if need_w else None
+    db = cut(bias_sum(gp)) if need_b else None
+    dx = None
+    if dx_dtype is not None:
+        dx = torch.empty(M, K, dtype=dx_dtype, device=g.device)
+        gemm(gl, wl, dx, M=M, N=K, K=Np, trans_b=True, ldb=K)
+    return dx, dw, db
+
+
 class LinearFn(torch.autograd.Function):
     """nn.Linear on f32 tokens (f32 in / f32 out; operands rounded to the compute dtype for the MFMA). An output width
     that is not a multiple of 8 (a classification head with 10 or 101 classes) runs zero-padded to the next multiple --
@@ -1017,30 +1058,15 @@ class LinearFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, w, b):
-        shp = x.shape
-        K = shp[-1]
-        N = w.shape[0]
-        Np = _pad8(N)
-        x2d = _chk(x.detach().contiguous(), torch.float32).view(-1, K)
-        M = x2d.shape[0]
+        shp, N = x.shape, w.shape[0]
+        x2d = _chk(x.detach().contiguous(), torch.float32).view(-1, shp[-1])
         xl = cast(x2d, _compute_dtype)
-        wl = lp_weight(w)
-        bias = b
-        if Np != N:
-            wp = torch.zeros(Np, K, dtype=wl.dtype, device=wl.device)
-            wp[:N].copy_(wl)
-            wl = wp
-            if b is not None:
-                bias = torch.zeros(Np, dtype=torch.float32, device=wl.device)
-                bias[:N].copy_(b.detach())
-        y = torch.empty(M, Np, dtype=torch.float32, device=x.device)
-        gemm(xl, wl, y, M=M, N=Np, K=K, bias=bias)
+        y, wl = _head_fwd(xl, lp_weight(w), b)
         ctx.save_for_backward(xl, wl)
-        ctx.has_bias = b is not None
         ctx.needs_dx = x.requires_grad
         ctx.prm = (w, b)
         ctx.n_out = N
-        if Np != N:
+        if wl.shape[0] != N:
             y = y[:, :N]
         return y.reshape(*shp[:-1], N)
 
@@ -1048,28 +1074,13 @@ class LinearFn(torch.autograd.Function):
     def backward(ctx, g):
         xl, wl = ctx.saved_tensors
         M, K = xl.shape
-        N, Np = ctx.n_out, wl.shape[0]
+        N = ctx.n_out
         g2d = _chk(g.contiguous(), torch.float32).view(M, N)
-        if Np != N:
-            gp = torch.zeros(M, Np, dtype=torch.float32, device=g.device)
-            gp[:, :N].copy_(g2d)
-            g2d = gp
-        gl = cast(g2d, xl.dtype)
-        dw = db = None
-        if Np == N:
-            dw = _wgrad(gl, xl, N, K, M, ctx.prm[0]) if ctx.needs_input_grad[1] else None
-            db = _bgrad(g2d, ctx.prm[1]) if (ctx.has_bias and ctx.needs_input_grad[2]) else None
-        else:
-            if ctx.needs_input_grad[1]:
-                dw = _wgrad(gl, xl, Np, K, M)[:N].contiguous()
-            if ctx.has_bias and ctx.needs_input_grad[2]:
-                db = colsum(g2d)[:N].contiguous()
-        dx = None
-        if ctx.needs_dx:
-            dx = torch.empty(M, K, dtype=torch.float32, device=g.device)
-            gemm(gl, wl, dx, M=M, N=K, K=Np, trans_b=True, ldb=K)
-            dx = dx.view(*g.shape[:-1], K)
-        return dx, dw, db
+        # the whole-width head queues its gradients on the parameters; the padded one has slices to cut first
+        wparam, bparam = ctx.prm if wl.shape[0] == N else (None, None)
+        dx, dw, db = _head_bwd(g2d, xl, wl, N, lambda gp: gp[:, :N].copy_(g2d), lambda gp: _bgrad(gp, bparam), wparam,
+                               ctx.needs_input_grad[1], ctx.needs_input_grad[2], torch.float32 if ctx.needs_dx else None)
+        return (None if dx is None else dx.view(*g.shape[:-1], K)), dw, db
 
 
 class UnshuffleFn(torch.autograd.Function):
@@ -1137,6 +1148,36 @@ def _pad8(n):
     return (n + 7) // 8 * 8
 
 
+def _bn_ws(R, N, device):
+    """Workspace of evp_batchnorm_fwd / _bwd on [R, N]: two partial rows per row block and two result rows."""
+    return torch.empty((2 * call("evp_batchnorm_nblk", R) + 2) * N, dtype=torch.float32, device=device)
+
+
+def _bn_train_fwd(y_pre, gamma, beta, running_mean, running_var, eps, momentum, relu):
+    """BatchNorm on the batch statistics of the rows of y_pre [R, N] (+ ReLU), in y_pre's dtype; the running statistics are updated in
+    place. -> (y, mean, invstd)."""
+    R, N = y_pre.shape
+    dev = y_pre.device
+    y = torch.empty(R, N, dtype=y_pre.dtype, device=dev)
+    mean, invstd = (torch.empty(N, dtype=torch.float32, device=dev) for _ in range(2))
+    ws = _bn_ws(R, N, dev)
+    call("evp_batchnorm_fwd", ptr(y_pre), dt(y_pre), R, N, ptr(gamma), ptr(beta), float(eps), float(momentum), int(relu),
+         ptr(y), ptr(mean), ptr(invstd), ptr(running_mean), ptr(running_var), ptr(ws), stream_ptr())
+    return y, mean, invstd
+
+
+def _bn_train_bwd(g, y_pre, y, gamma, mean, invstd, relu):
+    """Backward of _bn_train_fwd for g [R, N] in y's dtype -> (dpre, dgamma, dbeta); the last two None without gamma."""
+    R, N = y.shape
+    dev = g.device
+    dpre = torch.empty(R, N, dtype=y.dtype, device=dev)
+    dgamma, dbeta = (torch.empty(N, dtype=torch.float32, device=dev) if gamma is not None else None for _ in range(2))
+    ws = _bn_ws(R, N, dev)
+    call("evp_batchnorm_bwd", ptr(g), ptr(y_pre), ptr(y), dt(y), R, N, ptr(gamma), ptr(mean), ptr(invstd), int(relu),
+         ptr(dpre), ptr(dgamma), ptr(dbeta), ptr(ws), stream_ptr())
+    return dpre, dgamma, dbeta
+
+
 class LinearBNFn(torch.autograd.Function):
     """Linear(no bias) -> BatchNorm over the B*L token rows (training statistics) -> optional ReLU: one stage of the
     MoCo-v3 heads (mlp_head.py:4-24 applied as pr_hub_model.py:223-237). Hidden stages keep the compute dtype, the
@@ -1153,13 +1194,7 @@ class LinearBNFn(torch.autograd.Function):
         ydt = torch.float32 if last else T
         y_pre = torch.empty(R, N, dtype=ydt, device=dev)
         gemm(xl, wl, y_pre, M=R, N=N, K=K)
-        y = torch.empty(R, N, dtype=ydt, device=dev)
-        mean = torch.empty(N, dtype=torch.float32, device=dev)
-        invstd = torch.empty(N, dtype=torch.float32, device=dev)
-        nb = call("evp_batchnorm_nblk", R)
-        ws = torch.empty((2 * nb + 2) * N, dtype=torch.float32, device=dev)
-        call("evp_batchnorm_fwd", ptr(y_pre), dt(y_pre), R, N, ptr(gamma), ptr(beta), float(eps), float(momentum), int(relu),
-             ptr(y), ptr(mean), ptr(invstd), ptr(running_mean), ptr(running_var), ptr(ws), stream_ptr())
+        y, mean, invstd = _bn_train_fwd(y_pre, gamma, beta, running_mean, running_var, eps, momentum, relu)
         ctx.save_for_backward(xl, wl, y_pre, y, mean, invstd, gamma)
         ctx.cfg = (B, L, K, N, bool(relu), x.dtype, x.requires_grad)
         ctx.prm = (w,)
@@ -1170,21 +1205,13 @@ class LinearBNFn(torch.autograd.Function):
         xl, wl, y_pre, y, mean, invstd, gamma = ctx.saved_tensors
         B, L, K, N, relu, xdt, need_dx = ctx.cfg
         R = B * L
-        dev = g.device
         g2d = cast(_chk(g.contiguous()).view(R, N), y.dtype)
-        dpre = torch.empty(R, N, dtype=y.dtype, device=dev)
-        nb = call("evp_batchnorm_nblk", R)
-        ws = torch.empty((2 * nb + 2) * N, dtype=torch.float32, device=dev)
-        affine = gamma is not None
-        dgamma = torch.empty(N, dtype=torch.float32, device=dev) if affine else None
-        dbeta = torch.empty(N, dtype=torch.float32, device=dev) if affine else None
-        call("evp_batchnorm_bwd", ptr(g2d), ptr(y_pre), ptr(y), dt(y), R, N, ptr(gamma), ptr(mean), ptr(invstd), int(relu),
-             ptr(dpre), ptr(dgamma), ptr(dbeta), ptr(ws), stream_ptr())
+        dpre, dgamma, dbeta = _bn_train_bwd(g2d, y_pre, y, gamma, mean, invstd, relu)
         dl = cast(dpre, xl.dtype)
         dw = _wgrad(dl, xl, N, K, R, ctx.prm[0]) if ctx.needs_input_grad[1] else None
         dx = None
         if need_dx:
-            dx = torch.empty(R, K, dtype=xdt if xdt == torch.float32 else xl.dtype, device=dev)
+            dx = torch.empty(R, K, dtype=xdt if xdt == torch.float32 else xl.dtype, device=g.device)
             gemm(dl, wl, dx, M=R, N=K, K=N, trans_b=True, ldb=K)
             dx = dx.view(B, L, K)
         return dx, dw, dgamma, dbeta, None, None, None, None, None, None
@@ -1929,12 +1956,7 @@ class ConvBNFn(torch.autograd.Function):
         y_pre = torch.empty(R, N, dtype=T, device=dev)
         gemm(a, wl, y_pre, M=R, N=N, K=K, bias=b)
         if training:
-            y = torch.empty(R, N, dtype=T, device=dev)
-            mean = torch.empty(N, dtype=torch.float32, device=dev)
-            invstd = torch.empty(N, dtype=torch.float32, device=dev)
-            ws = torch.empty((2 * call("evp_batchnorm_nblk", R) + 2) * N, dtype=torch.float32, device=dev)
-            call("evp_batchnorm_fwd", ptr(y_pre), dt(y_pre), R, N, ptr(gamma), ptr(beta), float(eps), float(momentum), int(relu),
-                 ptr(y), ptr(mean), ptr(invstd), ptr(running_mean), ptr(running_var), ptr(ws), stream_ptr())
+            y, mean, invstd = _bn_train_fwd(y_pre, gamma, beta, running_mean, running_var, eps, momentum, relu)
             ret = y if out is None else map_copy(y, T, out)
             ctx.save_for_backward(a, wl, y_pre, y, mean, invstd, gamma)
         else:
@@ -1950,21 +1972,13 @@ class ConvBNFn(torch.autograd.Function):
     def backward(ctx, g):
         B, H, W, k, relu, training, eps, xdt, need_dx = ctx.cfg
         w, b = ctx.prm
-        R, dev = B * H * W, g.device
+        R, N, dev = B * H * W, w.shape[0], g.device
         dgamma = dbeta = None
         if training:
             a, wl, y_pre, y, mean, invstd, gamma = ctx.saved_tensors
-            N = y.shape[1]
-            gc = _contig(g, y.dtype)
-            dpre = torch.empty(R, N, dtype=y.dtype, device=dev)
-            ws = torch.empty((2 * call("evp_batchnorm_nblk", R) + 2) * N, dtype=torch.float32, device=dev)
-            dgamma = torch.empty(N, dtype=torch.float32, device=dev)
-            dbeta = torch.empty(N, dtype=torch.float32, device=dev)
-            call("evp_batchnorm_bwd", ptr(gc), ptr(y_pre), ptr(y), dt(y), R, N, ptr(gamma), ptr(mean), ptr(invstd), int(relu),
-                 ptr(dpre), ptr(dgamma), ptr(dbeta), ptr(ws), stream_ptr())
+            dpre, dgamma, dbeta = _bn_train_bwd(_contig(g, y.dtype), y_pre, y, gamma, mean, invstd, relu)
         else:
             a, wl, y, rvar, gamma = ctx.saved_tensors
-            N = y.shape[1]
             gm, ldg = _map(g)
             ym, ldy = _map(y)
             dpre = torch.empty(R, N, dtype=y.dtype, device=dev)
@@ -2080,26 +2094,15 @@ def draw_channel_scale(B, Cc, p, device, keep=None):
 
 class DenseClsFn(torch.autograd.Function):
     """The heads' `conv_dense` (nn.Conv2d(channels, out_channels, 1); ft_dense_decoder.py:41,48) on a map -> float32 [B*H*W, out_channels].
-    11 classes or 2 flow components run zero-padded to 8 columns, as LinearFn's narrow heads do; the bias gradient is an ordered sum."""
+    11 classes or 2 flow components run zero-padded to 8 columns (_head_fwd / _head_bwd, LinearFn's narrow heads); the bias gradient
+    is an ordered sum and nothing is queued."""
 
     @staticmethod
     def forward(ctx, x, w, b):
         T = _compute_dtype
         xl = _contig(x.detach(), T)
-        R, K = xl.shape
         N = w.shape[0]
-        Np = _pad8(N)
-        wl = lp_weight(w).view(N, K)
-        bias = b
-        if Np != N:
-            wp = torch.zeros(Np, K, dtype=wl.dtype, device=wl.device)
-            wp[:N].copy_(wl)
-            wl = wp
-            if b is not None:
-                bias = torch.zeros(Np, dtype=torch.float32, device=wl.device)
-                bias[:N].copy_(b.detach())
-        y = torch.empty(R, Np, dtype=torch.float32, device=x.device)
-        gemm(xl, wl, y, M=R, N=Np, K=K, bias=bias)
+        y, wl = _head_fwd(xl, lp_weight(w).view(N, xl.shape[1]), b)
         ctx.save_for_backward(xl, wl)
         ctx.cfg = (N, x.dtype, x.requires_grad, tuple(w.shape))
         return y[:, :N]
@@ -2108,19 +2111,6 @@ class DenseClsFn(torch.autograd.Function):
     def backward(ctx, g):
         xl, wl = ctx.saved_tensors
         N, xdt, need_dx, wshape = ctx.cfg
-        (R, K), Np = xl.shape, wl.shape[0]
-        if Np != N:
-            gp = torch.zeros(R, Np, dtype=torch.float32, device=g.device)
-            map_copy(g, torch.float32, (gp, 0))
-        else:
-            gp = _contig(g, torch.float32)
-        gl = cast(gp, xl.dtype)
-        dw = db = dx = None
-        if ctx.needs_input_grad[1]:
-            dw = _wgrad(gl, xl, Np, K, R)[:N].contiguous().view(wshape)
-        if ctx.needs_input_grad[2]:
-            db = colsum_ordered(gp)[:N].contiguous()
-        if need_dx:
-            dx = torch.empty(R, K, dtype=xdt, device=g.device)
-            gemm(gl, wl, dx, M=R, N=K, K=Np, trans_b=True, ldb=K)
-        return dx, dw, db
+        dx, dw, db = _head_bwd(g, xl, wl, N, lambda gp: map_copy(g, torch.float32, (gp, 0)), colsum_ordered, None,
+                               ctx.needs_input_grad[1], ctx.needs_input_grad[2], xdt if need_dx else None)
+        return dx, (None if dw is None else dw.view(wshape)), db
