@@ -145,8 +145,7 @@ struct UpsampleFwd {      // [B*h*w, C] -> row (b, y, x) of [B*H*W, C]
     const int64_t r0 = (int64_t)(p.b * h + ty.i0) * w, r1 = (int64_t)(p.b * h + ty.i1) * w;
     const float a = ld_any(in, in_dtype, (r0 + tx.i0) * ldi + c), bb = ld_any(in, in_dtype, (r0 + tx.i1) * ldi + c);
     const float cc = ld_any(in, in_dtype, (r1 + tx.i0) * ldi + c), d = ld_any(in, in_dtype, (r1 + tx.i1) * ldi + c);
-    const float top = fmaf(tx.l0, a, tx.l1 * bb), bot = fmaf(tx.l0, cc, tx.l1 * d);
-    return fmaf(ty.l0, top, ty.l1 * bot);
+    return tap_combine(ty, tx, a, bb, cc, d);
   }
 };
 

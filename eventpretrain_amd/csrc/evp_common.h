@@ -118,6 +118,11 @@ __device__ __forceinline__ Tap tap_of(int d, int n_in, float scale) {
   t.l0 = 1.f - t.l1;
   return t;
 }
+// the four taps a (i0y, i0x), b (i0y, i1x), c (i1y, i0x), d (i1y, i1x) combined: rows first, then the two rows (csrc/dense.hip: the map
+// resize; csrc/semseg.hip: the logits of an output pixel, which therefore equal the resized map's bit for bit)
+__device__ __forceinline__ float tap_combine(const Tap &ty, const Tap &tx, float a, float b, float c, float d) {
+  return fmaf(ty.l0, fmaf(tx.l0, a, tx.l1 * b), ty.l1 * fmaf(tx.l0, c, tx.l1 * d));
+}
 
 static inline int64_t ceil_div64(int64_t a, int64_t b) { return (a + b - 1) / b; }
 

@@ -2114,3 +2114,112 @@ class DenseClsFn(torch.autograd.Function):
         dx, dw, db = _head_bwd(g, xl, wl, N, lambda gp: map_copy(g, torch.float32, (gp, 0)), colsum_ordered, None,
                                ctx.needs_input_grad[1], ctx.needs_input_grad[2], xdt if need_dx else None)
         return dx, (None if dw is None else dw.view(wshape)), db
+
+
+# ----------------------------------------------------------------------------------------------------- segmentation objective
+# csrc/semseg.hip: cross entropy + Dice, and the evaluation's confusion table, from the LOW-RESOLUTION logits of a head. The logits of
+# an output pixel are interpolated in registers (resize_map's bits); the label map is the only full-resolution operand.
+_semseg_status = {}
+
+
+def semseg_status(device):
+    """int32 [1] in device memory: how many valid (not ignored) labels outside [0, num_classes) the segmentation kernels have met
+    since the last semseg_check_labels. Such pixels enter no sum; the count is read where the host reads back anyway."""
+    device = torch.device(device)
+    key = (device.type, torch.cuda.current_device() if device.index is None else device.index)
+    if key not in _semseg_status:
+        _semseg_status[key] = torch.zeros(1, dtype=torch.int32, device=device)
+    return _semseg_status[key]
+
+
+def semseg_check_labels(device):
+    """One read-back: raise if a label outside [0, num_classes) that is not the ignore label was met; the count starts again."""
+    st = semseg_status(device)
+    n = int(st.item())
+    if n:
+        st.zero_()
+        raise _lib.EvpError(f"segmentation labels: {n} pixels carry a label outside [0, num_classes) that is not the ignore label")
+
+
+def _semseg_operands(what, logits_map, B, h, w, label, ignore_label):
+    """-> (map read in place or a contiguous copy, ld, C, H, W, label, ignore value, has_ignore) of a segmentation call."""
+    for t in (logits_map, label):
+        if not t.is_cuda:
+            raise _lib.EvpError(f"{what}: tensor is not in device memory; eventpretrain_amd has no CPU path")
+    if logits_map.dim() != 2 or logits_map.dtype != torch.float32 or logits_map.shape[0] != B * h * w:
+        raise _lib.EvpError(f"{what}: logits must be a float32 map [B*h*w, C] = [{B * h * w}, C] (got {logits_map.dtype} {tuple(logits_map.shape)})")
+    C = logits_map.shape[1]
+    if not 2 <= C <= _lib.SEMSEG_MAX_CLASSES:
+        raise _lib.EvpError(f"{what}: {C} classes (2 to {_lib.SEMSEG_MAX_CLASSES} are supported)")
+    if label.dtype != torch.int64 or label.dim() != 4 or label.shape[0] != B or label.shape[1] != 1:
+        raise _lib.EvpError(f"{what}: label must be int64 [B, 1, H, W] with B = {B} (got {label.dtype} {tuple(label.shape)})")
+    H, W = int(label.shape[2]), int(label.shape[3])
+    if ignore_label is not None and 0 <= int(ignore_label) < C:
+        raise NotImplementedError(f"{what}: an ignore label inside [0, num_classes) (the reference then drops that class from the Dice sum)")
+    m = logits_map.detach()
+    ld = m.stride(0) if m.shape[0] > 1 else C
+    # in place only where every row, the last included, has ld floats behind it in the storage (a column slice of a padded matrix)
+    room = m.untyped_storage().nbytes() // 4 - m.storage_offset()
+    if m.stride(1) != 1 or ld < C or m.shape[0] * ld > room:
+        m, ld = m.contiguous(), C
+    return m, ld, C, H, W, label.contiguous(), (0 if ignore_label is None else int(ignore_label)), int(ignore_label is not None)
+
+
+def _semseg_workspace(P, device):
+    return torch.empty(call("evp_semseg_nblk", P) * _lib.SEMSEG_WS_ROW, dtype=torch.int32, device=device)
+
+
+class SemsegObjectiveFn(torch.autograd.Function):
+    """SemsegLoss of the reference (nn.CrossEntropyLoss(ignore_index) and the batch-wide Dice loss, trainer/finetune_semseg/
+    semseg_loss.py) applied to resize(logits, label size): (logits_map [B*h*w, C] float32, B, h, w, label int64 [B, 1, H, W],
+    ignore_label or None) -> (ce, dice), 0-d float32, differentiable in the map. The resized logits are never stored: forward is a
+    pixel pass and a finishing launch, backward one gather launch that writes the map's gradient (same leading dimension as the map,
+    pad columns zero). The map is read in place through its leading dimension (DenseClsFn's column slice of a padded matrix).
+    (h, w) == (H, W) is the reference's call form with logits already at label size: correct, but then every pixel is a map cell of
+    its own and the backward launches one wave per pixel; it is not meant to be fast."""
+
+    @staticmethod
+    def forward(ctx, logits_map, B, h, w, label, ignore_label=None):
+        m, ld, C, H, W, lab, ign, has = _semseg_operands("SemsegObjectiveFn", logits_map, B, h, w, label, ignore_label)
+        dev = m.device
+        out = torch.empty(2, dtype=torch.float32, device=dev)
+        saved = torch.empty(_lib.SEMSEG_SAVED, dtype=torch.float32, device=dev)
+        ws = _semseg_workspace(B * H * W, dev)
+        call("evp_semseg_objective_fwd", m.data_ptr(), ld, B, h, w, H, W, C, ptr(lab), ign, has, ptr(out), ptr(saved),
+             ptr(semseg_status(dev)), ptr(ws), stream_ptr())
+        ctx.save_for_backward(m, lab, saved)
+        ctx.cfg = (ld, B, h, w, H, W, C, ign, has)
+        return out[0], out[1]
+
+    @staticmethod
+    def backward(ctx, g_ce, g_dice):
+        m, lab, saved = ctx.saved_tensors
+        ld, B, h, w, H, W, C, ign, has = ctx.cfg
+        grad = torch.empty(B * h * w, ld, dtype=torch.float32, device=m.device)
+        call("evp_semseg_objective_bwd", m.data_ptr(), ld, B, h, w, H, W, C, ptr(lab), ign, has, ptr(saved),
+             ptr(_chk(g_ce.contiguous().view(1), torch.float32)), ptr(_chk(g_dice.contiguous().view(1), torch.float32)), ptr(grad), ld,
+             stream_ptr())
+        return (grad[:, :C],) + (None,) * 5
+
+
+def semseg_metrics(logits_map, B, h, w, label, ignore_label, table, cursor, confusion=None, argmax=None):
+    """The evaluation record of one segmentation batch on the device (evp_semseg_metrics; reference ft_semseg_trainer.py:207-241):
+    with s = cursor[0], table[s] = {ce + dice, mIoU, mAcc} of resize(logits, label size) against the labels, then cursor[0] = s + 1;
+    a full table is left alone. `confusion` (int64 [C, C], rows = label, columns = argmax) and `argmax` (uint8 [B, H, W], every pixel)
+    are filled when given. Arguments as SemsegObjectiveFn's; `table` float32 [capacity, 3] and `cursor` int64 [1] as cls_metrics'."""
+    for t in (table, cursor, confusion, argmax):
+        if t is not None and not t.is_cuda:
+            raise _lib.EvpError("semseg_metrics: tensor is not in device memory; eventpretrain_amd has no CPU path")
+    m, ld, C, H, W, lab, ign, has = _semseg_operands("semseg_metrics", logits_map, B, h, w, label, ignore_label)
+    if table.dim() != 2 or table.shape[1] != 3 or cursor.numel() != 1:
+        raise _lib.EvpError("semseg_metrics: table must be float32 [capacity, 3] and cursor one int64")
+    if confusion is not None and (tuple(confusion.shape) != (C, C) or not confusion.is_contiguous()):
+        raise _lib.EvpError(f"semseg_metrics: confusion must be a contiguous int64 [{C}, {C}] (got {tuple(confusion.shape)})")
+    if argmax is not None and (tuple(argmax.shape) != (B, H, W) or not argmax.is_contiguous()):
+        raise _lib.EvpError(f"semseg_metrics: argmax must be a contiguous uint8 [{B}, {H}, {W}] (got {tuple(argmax.shape)})")
+    dev = m.device
+    ws = _semseg_workspace(B * H * W, dev)
+    cws = torch.empty(call("evp_semseg_nblk", B * H * W) * C * C, dtype=torch.int32, device=dev)
+    call("evp_semseg_metrics", m.data_ptr(), ld, B, h, w, H, W, C, ptr(lab), ign, has, ptr(_chk(cursor, torch.int64)),
+         ptr(_chk(table, torch.float32)), table.shape[0], None if confusion is None else ptr(_chk(confusion, torch.int64)),
+         None if argmax is None else ptr(_chk(argmax, torch.uint8)), ptr(semseg_status(dev)), ptr(ws), ptr(cws), stream_ptr())

@@ -2,7 +2,10 @@
 its siblings, trainer/finetune_cls/ft_cls_trainer.py:15-108): set-up, per-iteration LR schedule, the step -- one HIP-graph replay
 through an engine.GraphedStep, or the eager forward + loss / accum_iter + scaler call -- the three ways of recording a loss, the
 TensorBoard rows, the visualisation hook, the close. trainer.pretrain.pr_trainer and trainer.finetune_cls.ft_cls_trainer pass in
-what differs between the phases: the loss names, the eager step, the executor builder."""
+what differs between the phases: the loss names, the eager step, the executor builder. val_loop_deferred is the evaluation loop of the
+fine-tuning trainers over a device metrics table."""
+import time
+
 import torch
 
 from ..utils import misc
@@ -83,6 +86,41 @@ class DeferredLosses:
         for v in vals:
             logger.update(**{name: v})
         return vals[-1]
+
+
+def val_loop_deferred(args, data_loader, logger, executor_for, meter_names):
+    """The evaluation loop with no host round-trip per batch: every batch is one executor.run (a HIP-graph replay; eager_with for a
+    batch of another shape) that leaves its three values in the executor's device table (engine.MetricsTable); the table is read back
+    and rewound when a progress line is due, when it is full and at the end of the loader, and every slot becomes one update per
+    meter, in batch order -- global_avg, the smoothed window and the returned dict are what per-batch updates give, the reference's
+    equal weight of a short last batch included. `meter_names`: the meters of the table's three columns, None for a column the
+    caller does not meter. A batch is (input, label, names). -> host seconds spent queueing the forwards."""
+    n_iter = len(data_loader)
+    executor, pending, infer_time = None, 0, 0.0
+
+    def flush():
+        for row in executor.table.read(pending):
+            for name, v in zip(meter_names, row):
+                if name is not None:
+                    logger.update(**{name: v})
+        return 0
+
+    for it, (x, label, _names) in enumerate(logger.log_every(args, data_loader, args.print_freq, "Test:")):
+        tensors = [x.to(args.device, non_blocking=True), label.to(args.device, non_blocking=True)]
+        if executor is None:
+            executor = executor_for(tensors)
+        t0 = time.time()
+        if all(tuple(t.shape) == tuple(s.shape) for t, s in zip(tensors, executor.inputs)):
+            executor.run(*tensors)
+        else:
+            executor.eager_with(*tensors)
+        infer_time += time.time() - t0
+        pending += 1
+        if (it + 1) % args.print_freq == 0 or pending >= executor.table.capacity or it + 1 == n_iter:
+            pending = flush()
+    if pending:              # (a loader that yields more batches than len() promised)
+        flush()
+    return infer_time
 
 
 def auto_executor(args, model, optimizer, loss_name, build, extra=()):

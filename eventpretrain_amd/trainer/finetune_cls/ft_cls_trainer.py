@@ -8,7 +8,7 @@ import torch
 
 from ... import ops
 from ...utils import misc
-from ..epoch import DevicePrefetcher, auto_executor, run_epoch
+from ..epoch import DevicePrefetcher, auto_executor, run_epoch, val_loop_deferred
 
 
 def _forward(args, model, x):
@@ -94,38 +94,8 @@ def _use_captured_eval(args, model):
 
 
 def _val_loop_deferred(args, data_loader, logger, executor_for, with_acc5):
-    """The evaluation loop with no host round-trip per batch: every batch is one executor.run (a HIP-graph replay; eager_with for a
-    batch of another shape) that leaves {loss, acc1, acc5} in the executor's device table; the table is read back and rewound when
-    a progress line is due, when it is full and at the end of the loader, and every slot becomes one update per meter, in batch
-    order -- global_avg, the smoothed window and the returned dict are what per-batch updates give, the reference's equal weight
-    of a short last batch included. -> host seconds spent queueing the forwards."""
-    n_iter = len(data_loader)
-    executor, pending, infer_time = None, 0, 0.0
-
-    def flush():
-        for loss, acc1, acc5 in executor.table.read(pending):
-            logger.update(loss_cls=loss)
-            logger.update(acc1=acc1)
-            if with_acc5:
-                logger.update(acc5=acc5)
-        return 0
-
-    for it, (events_voxel_grid, label, image_name) in enumerate(logger.log_every(args, data_loader, args.print_freq, "Test:")):
-        tensors = [events_voxel_grid.to(args.device, non_blocking=True), label.to(args.device, non_blocking=True)]
-        if executor is None:
-            executor = executor_for(tensors)
-        t0 = time.time()
-        if all(tuple(t.shape) == tuple(s.shape) for t, s in zip(tensors, executor.inputs)):
-            executor.run(*tensors)
-        else:
-            executor.eager_with(*tensors)
-        infer_time += time.time() - t0
-        pending += 1
-        if (it + 1) % args.print_freq == 0 or pending >= executor.table.capacity or it + 1 == n_iter:
-            pending = flush()
-    if pending:              # (a loader that yields more batches than len() promised)
-        flush()
-    return infer_time
+    """trainer.epoch.val_loop_deferred with this trainer's meters on the table's columns {loss, acc1, acc5}."""
+    return val_loop_deferred(args, data_loader, logger, executor_for, ("loss_cls", "acc1", "acc5" if with_acc5 else None))
 
 
 def _val_loop_eager(args, model, data_loader, logger, with_acc5):

@@ -103,6 +103,8 @@ class MetricLogger:
         prints progress every print_freq iterations."""
         if args.phase == "finetune_cls":
             keys = ("events_voxel_grid", "label", "image_name")
+        elif args.phase == "finetune_semseg":
+            keys = ("events_voxel_grid", "semseg_label", "seq_name")
         elif args.phase == "pretrain" and args.pr_phase in _BATCH_KEYS:
             keys = _BATCH_KEYS[args.pr_phase]
         else:

@@ -32,7 +32,7 @@ enum { EVP_ACT_NONE = 0, EVP_ACT_GELU = 1, EVP_ACT_DGELU = 2, EVP_ACT_RELU = 3, 
 const char *evp_last_error(void);
 /* ABI version of this header; bumped on any signature change (2: evp_dropout_fwd takes a device-side seed; evp_gemm_desc lost its
  * stream-K workspace fields in round 3; 3: evp_events_draw_erase_add; 4: keep flags on the window attention; 5: evp_events_plan_batch; entries ADDED since -- evp_cls_metrics,
- * evp_view_augment_bilinear_f32, evp_voxel_scatter_fused_algo_f32, evp_events_window_geometry, evp_events_build_added_hw_f64 -- change no signature and keep 5). A host binding must compare evp_abi_version() with EVP_ABI_VERSION at load time. */
+ * evp_view_augment_bilinear_f32, evp_voxel_scatter_fused_algo_f32, evp_events_window_geometry, evp_events_build_added_hw_f64, evp_semseg_* -- change no signature and keep 5). A host binding must compare evp_abi_version() with EVP_ABI_VERSION at load time. */
 #define EVP_ABI_VERSION 5
 int evp_abi_version(void);
 /* Name of the code object's target ("gfx950"). */
@@ -647,6 +647,38 @@ int evp_batchnorm_eval_bwd(const void *g, int g_dtype, int64_t ldg, const void *
                            const float *gamma, const float *running_var, float eps, int relu, void *dx, int dx_dtype, int64_t ldx,
                            void *stream);
 int evp_colsum_ordered(const void *x, int dtype, int64_t R, int C, int64_t ld, float *out, void *stream);
+
+/* ------------------------------------------------------------------------------------------------ K27 segmentation objective
+ * The objective and the metrics of semantic-segmentation fine-tuning (trainer/finetune_semseg/semseg_loss.py, semseg_metric.py as
+ * ft_semseg_trainer.py calls them) computed from the LOW-RESOLUTION logits: map float32 [B*h*w, ld] (C valid columns, 2 <= C <=
+ * EVP_SEMSEG_MAX_CLASSES, read in place), label int64 [B,1,H,W]. The logits of output pixel (b, y, x) are the align_corners = False
+ * bilinear interpolation of the map (tap for tap and bit for bit evp_upsample_bilinear_fwd's; (h, w) == (H, W): the map itself) and are
+ * never stored. A pixel is valid when its label is not ignore_label (has_ignore == 0: nothing is ignored); a valid pixel whose label
+ * lies outside [0, C) is an input error: it enters no sum and is counted into *status (int32, device memory, += per call; may be NULL).
+ * With p = softmax of a valid pixel's logits, y its label, sums over the valid pixels of the WHOLE batch:
+ *   ce    = sum(logsumexp - z[y]) / n_valid                       (NaN when nothing is valid, as nn.CrossEntropyLoss)
+ *   dice  = (1/C) sum_c [1 - N_c / D_c],  N_c = 2 sum p_c [y = c] + 1,  D_c = sum p_c^2 + #{y = c} + 1
+ * evp_semseg_objective_fwd: out[0] = ce, out[1] = dice; saved float32 [EVP_SEMSEG_SAVED] = {n_valid, N_c (32), D_c (32)} for the backward.
+ * evp_semseg_objective_bwd: grad float32 [B*h*w, ldg] (ldg >= C, columns C.. written as zero) = d(g_ce[0] * ce + g_dice[0] * dice)/d map;
+ *   g_ce, g_dice one float each in DEVICE memory. A gather: one workgroup per map cell walks the pixels whose taps name the cell.
+ * evp_semseg_metrics: the same pixel pass also takes argmax_c z (first maximum) and counts confusion[label, argmax] over the valid pixels;
+ *   writes confusion int64 [C,C] (optional), argmax uint8 [B,H,W] (optional, every pixel), and with s = *cursor, 0 <= s < capacity:
+ *   table[s] = {ce + dice, mIoU, mAcc}, *cursor = s + 1 (as evp_cls_metrics), mIoU = mean_c 100 diag / max(row + col - diag, 1e-12),
+ *   mAcc = mean_c 100 diag / max(row, 1e-12) over all C classes in double, rounded to float32 once.
+ * workspace: uint32 [evp_semseg_nblk(B*H*W) * EVP_SEMSEG_WS_ROW]; conf_workspace: int32 [evp_semseg_nblk(B*H*W) * C * C].
+ * No float atomics: partial sums go wave -> LDS -> one workspace row per workgroup -> a sum in fixed order, in double. */
+#define EVP_SEMSEG_MAX_CLASSES 32
+#define EVP_SEMSEG_WS_ROW 100
+#define EVP_SEMSEG_SAVED 68
+int evp_semseg_nblk(int64_t pixels);
+int evp_semseg_objective_fwd(const float *map, int64_t ld, int B, int h, int w, int H, int W, int C, const int64_t *label,
+                             int64_t ignore_label, int has_ignore, float *out, float *saved, int32_t *status, void *workspace, void *stream);
+int evp_semseg_objective_bwd(const float *map, int64_t ld, int B, int h, int w, int H, int W, int C, const int64_t *label,
+                             int64_t ignore_label, int has_ignore, const float *saved, const float *g_ce, const float *g_dice, float *grad,
+                             int64_t ldg, void *stream);
+int evp_semseg_metrics(const float *map, int64_t ld, int B, int h, int w, int H, int W, int C, const int64_t *label, int64_t ignore_label,
+                       int has_ignore, int64_t *cursor, float *table, int64_t capacity, int64_t *confusion, uint8_t *argmax, int32_t *status,
+                       void *workspace, void *conf_workspace, void *stream);
 
 #ifdef __cplusplus
 }
