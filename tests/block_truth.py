@@ -16,7 +16,8 @@ Gates, all measured against the yardstick, FACTOR being the only constant:
      family of blocks of the same tensor. Families: 16 x 64 tiles of [M, D] tensors (output, dx), 128 x 128 tiles of weight
      gradients, the (sample, head) slices of an attention map, and for the qkv weight / bias gradients the q, k, v thirds and each
      head's slice of each third (bias: q and v only, see families()). Blocks whose truth norm is below FLOOR of the family's RMS block norm are left out (dropped samples,
-     masked positions); at most MAX_EXCLUDED of a family may be left out -- a condition on the INPUTS, asserted.
+     masked positions); at most MAX_EXCLUDED of a family may be left out -- a condition on the INPUTS, asserted. The tensors of the
+     attention cores ("core:...", tests/attention_truth.py) have families of their own, _core_families.
   3. scale         |<got, T> / <T, T> - 1| <= FACTOR * e_ref. Rounding noise is near zero-mean; a missing 1 / keep_prob, 1 / R or
      d_h^-0.5 is not.
 The yardstick is computed here at run time (milliseconds at these shapes), never from the code under test."""
@@ -223,10 +224,38 @@ def _tiles(shape, tile):
             for r in range(0, shape[0], tile[0]) for c in range(0, shape[1], tile[1])]
 
 
+CORE_STRIP = 16         # rows of one query / key strip of the fused attention kernels
+
+
+def _core_families(kind, shape):
+    """The tensors of an attention core, handed over as [B, heads, N, d_h] (out and the q, k, v thirds of dqkv), [B, heads, N] (lse),
+    [B, heads, N, N] (attn), [R, heads] (dtable), and anything else (dqkv as a whole) without sub-blocks."""
+    fam = {}
+    if kind in ("out", "dq", "dk", "dv"):
+        planes, N = shape[0] * shape[1], shape[2]
+        v = (planes * N, shape[3])
+        fam["head"] = [(slice(p * N, (p + 1) * N), slice(0, v[1])) for p in range(planes)]
+        fam["strip16"] = [(slice(p * N + r, p * N + min(r + CORE_STRIP, N)), slice(0, v[1])) for p in range(planes) for r in range(0, N, CORE_STRIP)]
+    elif kind == "lse":
+        v = (shape[0] * shape[1], shape[2])
+        fam["head"] = [(slice(p, p + 1), slice(0, v[1])) for p in range(v[0])]
+    elif kind == "attn":
+        v = (math.prod(shape[:-1]), shape[-1])
+        fam["head"] = [(slice(r, r + shape[-2]), slice(0, shape[-1])) for r in range(0, v[0], shape[-2])]
+    elif kind == "dtable":
+        v = tuple(shape)
+        fam["head_col"] = [(slice(0, v[0]), slice(h, h + 1)) for h in range(v[1])]
+    else:
+        v = (math.prod(shape), 1)
+    return v, fam
+
+
 def families(tensor, shape, heads=None):
     """-> (the 2-D view's shape, {family: [(row slice, column slice), ...]}) for the tensor called `tensor`."""
     fam = {}
-    if tensor in ("out", "dx") or tensor.startswith("act:"):       # "act:...": the [M, D] tensors of tests/contrast_truth.py
+    if tensor.startswith("core:"):                   # the attention cores' own tensors (tests/attention_truth.py), [B, heads, N, ...]
+        return _core_families(tensor[5:], shape)
+    if tensor in ("out", "dx") or tensor.startswith("act:"):      # "act:...": the [M, D] tensors of tests/contrast_truth.py
         v = (math.prod(shape[:-1]), shape[-1])
         fam["tile16x64"] = _tiles(v, ACT_TILE)
     elif tensor == "attn":

@@ -29,13 +29,20 @@ import torch
 HERE = os.path.dirname(os.path.abspath(__file__))
 GOLDEN = os.path.join(HERE, "golden", "block_launch_trace.json")
 
+def _win_nchunk(Bg, nG, heads, target=512):
+    """win_chunks of csrc/attention_fused.hip (tests/test_gpu_attention_truth.py holds this formula against the library's answer)."""
+    B = Bg // nG
+    per = -(-B // max(1, min(B, -(-target // (nG * heads)))))
+    return -(-B // per)
+
+
 # answers of the count queries (the entries that launch nothing and return a size): fixed here, the library is never loaded
 COUNT_QUERIES = {
     "evp_layernorm_bwd_nblk": lambda M: 3,
     "evp_colsum_nblk": lambda M: 2,
     "evp_attention_fused_supported": lambda code, N, dh: int(code == 1 and N <= 224 and dh in (32, 64)),
     "evp_window_attention_fused_np": lambda N: 32 if N <= 32 else 64 if N <= 64 else 96 if N <= 96 else 128,
-    "evp_window_attention_fused_nchunk": lambda Bg, nG, heads: 2,
+    "evp_window_attention_fused_nchunk": lambda Bg, nG, heads: _win_nchunk(Bg, nG, heads),
     "evp_dwconv5x5_bwd_nslab": lambda B, H, W: 5,
 }
 _STREAM = object()
