@@ -2141,6 +2141,18 @@ def semseg_check_labels(device):
         raise _lib.EvpError(f"segmentation labels: {n} pixels carry a label outside [0, num_classes) that is not the ignore label")
 
 
+def _map_in_place(x):
+    """float32 [R, C] -> (the map read where it lies, its leading dimension), or (a contiguous copy, C). In place only where every row,
+    the last included, has ld floats behind it in the storage (a column slice of a padded matrix)."""
+    m = x.detach()
+    C = m.shape[1]
+    ld = m.stride(0) if m.shape[0] > 1 else C
+    room = m.untyped_storage().nbytes() // 4 - m.storage_offset()
+    if m.stride(1) != 1 or ld < C or m.shape[0] * ld > room:
+        m, ld = m.contiguous(), C
+    return m, ld
+
+
 def _semseg_operands(what, logits_map, B, h, w, label, ignore_label):
     """-> (map read in place or a contiguous copy, ld, C, H, W, label, ignore value, has_ignore) of a segmentation call."""
     for t in (logits_map, label):
@@ -2156,12 +2168,7 @@ def _semseg_operands(what, logits_map, B, h, w, label, ignore_label):
     H, W = int(label.shape[2]), int(label.shape[3])
     if ignore_label is not None and 0 <= int(ignore_label) < C:
         raise NotImplementedError(f"{what}: an ignore label inside [0, num_classes) (the reference then drops that class from the Dice sum)")
-    m = logits_map.detach()
-    ld = m.stride(0) if m.shape[0] > 1 else C
-    # in place only where every row, the last included, has ld floats behind it in the storage (a column slice of a padded matrix)
-    room = m.untyped_storage().nbytes() // 4 - m.storage_offset()
-    if m.stride(1) != 1 or ld < C or m.shape[0] * ld > room:
-        m, ld = m.contiguous(), C
+    m, ld = _map_in_place(logits_map)
     return m, ld, C, H, W, label.contiguous(), (0 if ignore_label is None else int(ignore_label)), int(ignore_label is not None)
 
 
@@ -2223,3 +2230,80 @@ def semseg_metrics(logits_map, B, h, w, label, ignore_label, table, cursor, conf
     call("evp_semseg_metrics", m.data_ptr(), ld, B, h, w, H, W, C, ptr(lab), ign, has, ptr(_chk(cursor, torch.int64)),
          ptr(_chk(table, torch.float32)), table.shape[0], None if confusion is None else ptr(_chk(confusion, torch.int64)),
          None if argmax is None else ptr(_chk(argmax, torch.uint8)), ptr(semseg_status(dev)), ptr(ws), ptr(cws), stream_ptr())
+
+
+# ------------------------------------------------------------------------------------------------------ optical-flow objective
+# csrc/flow.hip: the masked L1 loss, and the validation's end-point error and outlier share, from the LOW-RESOLUTION two-channel
+# prediction of a head. A pixel's prediction is interpolated and scaled in registers (resize_flow); the labels are the only
+# full-resolution operands.
+def _flow_operands(what, flow_map, B, h, w, target, valid):
+    """-> (map read in place or a contiguous copy, ld, H, W, target, valid) of a flow call."""
+    for t in (flow_map, target, valid):
+        if not t.is_cuda:
+            raise _lib.EvpError(f"{what}: tensor is not in device memory; eventpretrain_amd has no CPU path")
+    if flow_map.dim() != 2 or flow_map.dtype != torch.float32 or tuple(flow_map.shape) != (B * h * w, 2):
+        raise _lib.EvpError(f"{what}: the prediction must be a float32 map [B*h*w, 2] = [{B * h * w}, 2] (got {flow_map.dtype} {tuple(flow_map.shape)})")
+    if target.dtype != torch.float32 or target.dim() != 4 or target.shape[0] != B or target.shape[1] != 2:
+        raise _lib.EvpError(f"{what}: target must be float32 [B, 2, H, W] with B = {B} (got {target.dtype} {tuple(target.shape)})")
+    H, W = int(target.shape[2]), int(target.shape[3])
+    if valid.dtype != torch.float32:
+        valid = valid.float()
+    if tuple(valid.shape) != (B, 1, H, W):
+        raise _lib.EvpError(f"{what}: valid must be [B, 1, H, W] = [{B}, 1, {H}, {W}] (got {tuple(valid.shape)})")
+    m, ld = _map_in_place(flow_map)
+    return m, ld, H, W, target.contiguous(), valid.contiguous()
+
+
+def _flow_workspace(P, device):
+    return torch.empty(call("evp_flow_nblk", P) * _lib.FLOW_WS_ROW, dtype=torch.int32, device=device)
+
+
+class FlowObjectiveFn(torch.autograd.Function):
+    """FlowLoss of the reference (trainer/finetune_flow/flow_loss.py) applied to resize_flow(prediction, label size): (flow_map
+    [B*h*w, 2] float32, B, h, w, target float32 [B, 2, H, W], valid [B, 1, H, W], max_flow) -> the mean of |p - t| over both
+    components of the pixels with valid >= 0.5 and |t| < max_flow, 0-d float32, differentiable in the map; NaN with an all-zero
+    gradient when no pixel is valid. The resized prediction is never stored: forward is a pixel pass and a finishing launch, backward
+    one gather launch that writes the map's gradient (same leading dimension as the map, pad columns zero). The map is read in place
+    through its leading dimension (DenseClsFn's column slice of a padded matrix)."""
+
+    @staticmethod
+    def forward(ctx, flow_map, B, h, w, target, valid, max_flow):
+        m, ld, H, W, tgt, val = _flow_operands("FlowObjectiveFn", flow_map, B, h, w, target, valid)
+        dev = m.device
+        out = torch.empty(1, dtype=torch.float32, device=dev)
+        saved = torch.empty(_lib.FLOW_SAVED, dtype=torch.float32, device=dev)
+        ws = _flow_workspace(B * H * W, dev)
+        call("evp_flow_objective_fwd", m.data_ptr(), ld, B, h, w, H, W, ptr(tgt), ptr(val), float(max_flow), ptr(out), ptr(saved), ptr(ws),
+             stream_ptr())
+        ctx.save_for_backward(m, tgt, val, saved)
+        ctx.cfg = (ld, B, h, w, H, W, float(max_flow))
+        return out[0]
+
+    @staticmethod
+    def backward(ctx, g_loss):
+        m, tgt, val, saved = ctx.saved_tensors
+        ld, B, h, w, H, W, max_flow = ctx.cfg
+        grad = torch.empty(B * h * w, ld, dtype=torch.float32, device=m.device)
+        call("evp_flow_objective_bwd", m.data_ptr(), ld, B, h, w, H, W, ptr(tgt), ptr(val), max_flow, ptr(saved),
+             ptr(_chk(g_loss.contiguous().view(1), torch.float32)), ptr(grad), ld, stream_ptr())
+        return (grad[:, :2],) + (None,) * 6
+
+
+def flow_metrics(flow_map, B, h, w, target, valid, max_flow, org, table, cursor):
+    """The evaluation record of one flow batch on the device (evp_flow_metrics; reference ft_flow_trainer.py:191-231): with
+    s = cursor[0], table[s] = {l1 (FlowObjectiveFn's bits), aee, outlier} of resize_flow(prediction, label size) over the sparse mask
+    -- valid non-zero and an event in `org` (float32 [B, C, H, W], the unnormalised voxel grid) at the pixel -- then cursor[0] = s + 1;
+    a full table is left alone. Arguments as FlowObjectiveFn's; `table` float32 [capacity, 3] and `cursor` int64 [1] as cls_metrics'."""
+    for t in (org, table, cursor):
+        if not t.is_cuda:
+            raise _lib.EvpError("flow_metrics: tensor is not in device memory; eventpretrain_amd has no CPU path")
+    m, ld, H, W, tgt, val = _flow_operands("flow_metrics", flow_map, B, h, w, target, valid)
+    if org.dim() != 4 or org.shape[0] != B or tuple(org.shape[2:]) != (H, W):
+        raise ValueError(f"flow_metrics: the event grid must be [B, C, H, W] at the label's size [{B}, C, {H}, {W}] (got {tuple(org.shape)})")
+    if org.dtype != torch.float32:
+        raise _lib.EvpError(f"flow_metrics: the event grid must be float32 (got {org.dtype})")
+    if table.dim() != 2 or table.shape[1] != 3 or cursor.numel() != 1:
+        raise _lib.EvpError("flow_metrics: table must be float32 [capacity, 3] and cursor one int64")
+    ws = _flow_workspace(B * H * W, m.device)
+    call("evp_flow_metrics", m.data_ptr(), ld, B, h, w, H, W, ptr(tgt), ptr(val), float(max_flow), ptr(org.contiguous()), int(org.shape[1]),
+         ptr(_chk(cursor, torch.int64)), ptr(_chk(table, torch.float32)), table.shape[0], ptr(ws), stream_ptr())

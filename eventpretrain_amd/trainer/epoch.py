@@ -94,7 +94,8 @@ def val_loop_deferred(args, data_loader, logger, executor_for, meter_names):
     and rewound when a progress line is due, when it is full and at the end of the loader, and every slot becomes one update per
     meter, in batch order -- global_avg, the smoothed window and the returned dict are what per-batch updates give, the reference's
     equal weight of a short last batch included. `meter_names`: the meters of the table's three columns, None for a column the
-    caller does not meter. A batch is (input, label, names). -> host seconds spent queueing the forwards."""
+    caller does not meter. A batch is the executor's tensors in order -- (input, label), or (input, events, label, valid) for flow --
+    then the names. -> host seconds spent queueing the forwards."""
     n_iter = len(data_loader)
     executor, pending, infer_time = None, 0, 0.0
 
@@ -105,8 +106,8 @@ def val_loop_deferred(args, data_loader, logger, executor_for, meter_names):
                     logger.update(**{name: v})
         return 0
 
-    for it, (x, label, _names) in enumerate(logger.log_every(args, data_loader, args.print_freq, "Test:")):
-        tensors = [x.to(args.device, non_blocking=True), label.to(args.device, non_blocking=True)]
+    for it, batch in enumerate(logger.log_every(args, data_loader, args.print_freq, "Test:")):
+        tensors = [t.to(args.device, non_blocking=True) for t in batch[:-1]]
         if executor is None:
             executor = executor_for(tensors)
         t0 = time.time()
@@ -154,9 +155,11 @@ def _executor_step(args, executor, tensors):
 
 
 def run_epoch(args, model, data_loader, optimizer, epoch, loss_scaler, log_writer, loss_names, eager_step, build_executor=None,
-              step_executor=None, clip_grad=None, meter_divided=False, vis_hook=None, vis_last_batch=True):
+              step_executor=None, clip_grad=None, meter_divided=False, vis_hook=None, vis_last_batch=True, batch_keys=None):
     """One training epoch -> {meter: global_avg}. A batch is the tuple misc.MetricLogger.log_every yields: tensors, then the sample names.
 
+    batch_keys      the keys of the loader's dict batches that make up that tuple, where they are not the phase's own (flow: the
+                    step takes no events_voxel_grid_org).
     loss_names      the meters / TensorBoard tags, in the order the eager step returns the losses.
     eager_step      (tensors, names) -> (losses, vis): the forward(s) of one batch; `vis` is what vis_hook takes between args and epoch.
                     The loop sums the losses, divides by accum_iter and hands the result to loss_scaler with `clip_grad`.
@@ -172,7 +175,7 @@ def run_epoch(args, model, data_loader, optimizer, epoch, loss_scaler, log_write
     skip = bool(getattr(args, "skip_nonfinite", False))
     if not skip:
         return _run_epoch(args, model, data_loader, optimizer, epoch, loss_scaler, log_writer, loss_names, eager_step, build_executor,
-                          step_executor, clip_grad, meter_divided, vis_hook, vis_last_batch)
+                          step_executor, clip_grad, meter_divided, vis_hook, vis_last_batch, batch_keys)
     if not hasattr(optimizer, "skip_nonfinite"):
         raise ValueError("args.skip_nonfinite needs a FusedAdamW (the verdict is reached on the device, inside the optimizer's launch)")
     if step_executor is not None and not getattr(step_executor, "skip_nonfinite", False):
@@ -181,7 +184,7 @@ def run_epoch(args, model, data_loader, optimizer, epoch, loss_scaler, log_write
     saved, optimizer.skip_nonfinite = optimizer.skip_nonfinite, True      # the eager steps of this epoch guard too
     try:
         stats = _run_epoch(args, model, data_loader, optimizer, epoch, loss_scaler, log_writer, loss_names, eager_step, build_executor,
-                           step_executor, clip_grad, meter_divided, vis_hook, vis_last_batch)
+                           step_executor, clip_grad, meter_divided, vis_hook, vis_last_batch, batch_keys)
     finally:
         optimizer.skip_nonfinite = saved
     stats["skipped_steps"] = optimizer.skipped_steps() - before
@@ -189,7 +192,7 @@ def run_epoch(args, model, data_loader, optimizer, epoch, loss_scaler, log_write
 
 
 def _run_epoch(args, model, data_loader, optimizer, epoch, loss_scaler, log_writer, loss_names, eager_step, build_executor,
-               step_executor, clip_grad, meter_divided, vis_hook, vis_last_batch):
+               step_executor, clip_grad, meter_divided, vis_hook, vis_last_batch, batch_keys=None):
     model.train(True)
     logger = misc.MetricLogger(delimiter="  ")
     logger.add_meter("lr", misc.SmoothedValue(window_size=1, fmt="{value:.6f}"))
@@ -218,7 +221,7 @@ def _run_epoch(args, model, data_loader, optimizer, epoch, loss_scaler, log_writ
             log_writer.add_scalar(name, v, x)
         log_writer.add_scalar("lr", lr, x)
 
-    for it, batch in enumerate(logger.log_every(args, data_loader, args.print_freq, header)):
+    for it, batch in enumerate(logger.log_every(args, data_loader, args.print_freq, header, keys=batch_keys)):
         if it % args.accum_iter == 0:
             adjust_learning_rate(optimizer, it / n_iter + epoch, args)
         tensors = [t.to(args.device, non_blocking=True) for t in batch[:-1]]

@@ -66,6 +66,8 @@ _BATCH_KEYS = {
     "adj-n": ("events_voxel_grid", "image", "image_name"), "con-n": ("events_voxel_grid", "image", "image_name"),
     "rec+con": ("events_voxel_grid", "sub_frame", "clip_emb", "image_name"),
 }
+# phase finetune_flow (reference utils/misc.py:163-165); events_voxel_grid_org feeds the validation's events mask alone
+FLOW_BATCH_KEYS = ("events_voxel_grid", "events_voxel_grid_org", "flow_label", "flow_label_valid", "seq_name")
 
 
 class MetricLogger:
@@ -98,13 +100,17 @@ class MetricLogger:
     def add_meter(self, name, meter):
         self.meters[name] = meter
 
-    def log_every(self, args, iterable, print_freq, header=None):
+    def log_every(self, args, iterable, print_freq, header=None, keys=None):
         """Yields each batch dict as the tuple the phase's trainer unpacks (reference utils/misc.py:144-167) and
-        prints progress every print_freq iterations."""
-        if args.phase == "finetune_cls":
+        prints progress every print_freq iterations. `keys`: the caller's own selection in place of the phase's."""
+        if keys is not None:
+            keys = tuple(keys)
+        elif args.phase == "finetune_cls":
             keys = ("events_voxel_grid", "label", "image_name")
         elif args.phase == "finetune_semseg":
             keys = ("events_voxel_grid", "semseg_label", "seq_name")
+        elif args.phase == "finetune_flow":
+            keys = FLOW_BATCH_KEYS
         elif args.phase == "pretrain" and args.pr_phase in _BATCH_KEYS:
             keys = _BATCH_KEYS[args.pr_phase]
         else:

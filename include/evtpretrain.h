@@ -32,7 +32,7 @@ enum { EVP_ACT_NONE = 0, EVP_ACT_GELU = 1, EVP_ACT_DGELU = 2, EVP_ACT_RELU = 3, 
 const char *evp_last_error(void);
 /* ABI version of this header; bumped on any signature change (2: evp_dropout_fwd takes a device-side seed; evp_gemm_desc lost its
  * stream-K workspace fields in round 3; 3: evp_events_draw_erase_add; 4: keep flags on the window attention; 5: evp_events_plan_batch; entries ADDED since -- evp_cls_metrics,
- * evp_view_augment_bilinear_f32, evp_voxel_scatter_fused_algo_f32, evp_events_window_geometry, evp_events_build_added_hw_f64, evp_semseg_* -- change no signature and keep 5). A host binding must compare evp_abi_version() with EVP_ABI_VERSION at load time. */
+ * evp_view_augment_bilinear_f32, evp_voxel_scatter_fused_algo_f32, evp_events_window_geometry, evp_events_build_added_hw_f64, evp_semseg_*, evp_flow_* -- change no signature and keep 5). A host binding must compare evp_abi_version() with EVP_ABI_VERSION at load time. */
 #define EVP_ABI_VERSION 5
 int evp_abi_version(void);
 /* Name of the code object's target ("gfx950"). */
@@ -679,6 +679,36 @@ int evp_semseg_objective_bwd(const float *map, int64_t ld, int B, int h, int w, 
 int evp_semseg_metrics(const float *map, int64_t ld, int B, int h, int w, int H, int W, int C, const int64_t *label, int64_t ignore_label,
                        int has_ignore, int64_t *cursor, float *table, int64_t capacity, int64_t *confusion, uint8_t *argmax, int32_t *status,
                        void *workspace, void *conf_workspace, void *stream);
+
+/* ------------------------------------------------------------------------------------------------ K28 optical-flow objective
+ * The objective and the metrics of optical-flow fine-tuning (trainer/finetune_flow/flow_loss.py, flow_metric.py as ft_flow_trainer.py
+ * calls them, behind utils/reshape.py resize_flow) computed from the LOW-RESOLUTION prediction: map float32 [B*h*w, ld] (columns 0, 1 =
+ * the x and y components, ld >= 2, read in place), target float32 [B,2,H,W], valid float32 [B,1,H,W]. The prediction of output pixel
+ * (b, y, x) is the align_corners = False bilinear interpolation of the map (tap for tap and bit for bit evp_upsample_bilinear_fwd's;
+ * (h, w) == (H, W): the map itself) with x times (float)(W / w) and y times (float)(H / h), the quotients taken in double; it is
+ * never stored. With mag = sqrt(tx^2 + ty^2) in float32, sums over the WHOLE batch:
+ *   loss mask    valid >= 0.5 and mag < max_flow;         l1 = sum(|px - tx| + |py - ty|) / (2 n)          (NaN when n = 0)
+ *   sparse mask  valid != 0 and the float32 sum of squares of org[b, :, y, x] > 0 (max_flow is NOT applied);  epe = |p - t|_2
+ *                aee = sum(epe) / n_sparse,  outlier = 100 #{epe > 3 and epe / mag > 0.05} / n_sparse      (NaN when n_sparse = 0)
+ * evp_flow_objective_fwd: out[0] = l1; saved float32 [EVP_FLOW_SAVED] = {n} for the backward.
+ * evp_flow_objective_bwd: grad float32 [B*h*w, ldg] (ldg >= 2, columns 2.. written as zero) = g_loss[0] * d l1 / d map, g_loss one
+ *   float in DEVICE memory; sign(0) = 0; n = 0 gives exact zeros. A gather: one workgroup per map cell walks the pixels whose taps
+ *   name the cell.
+ * evp_flow_metrics: org float32 [B, org_channels, H, W]; with s = *cursor, 0 <= s < capacity: table[s] = {l1, aee, outlier},
+ *   *cursor = s + 1 (as evp_cls_metrics); a full table or a cursor outside [0, capacity) leaves both untouched. l1 has the bits of
+ *   evp_flow_objective_fwd's.
+ * workspace: uint32 [evp_flow_nblk(B*H*W) * EVP_FLOW_WS_ROW].
+ * No float atomics: partial sums go wave -> LDS -> one workspace row per workgroup -> a sum in fixed order, in double. */
+#define EVP_FLOW_WS_ROW 8
+#define EVP_FLOW_SAVED 4
+int evp_flow_nblk(int64_t pixels);
+int evp_flow_objective_fwd(const float *map, int64_t ld, int B, int h, int w, int H, int W, const float *target, const float *valid,
+                           float max_flow, float *out, float *saved, void *workspace, void *stream);
+int evp_flow_objective_bwd(const float *map, int64_t ld, int B, int h, int w, int H, int W, const float *target, const float *valid,
+                           float max_flow, const float *saved, const float *g_loss, float *grad, int64_t ldg, void *stream);
+int evp_flow_metrics(const float *map, int64_t ld, int B, int h, int w, int H, int W, const float *target, const float *valid,
+                     float max_flow, const float *org, int org_channels, int64_t *cursor, float *table, int64_t capacity, void *workspace,
+                     void *stream);
 
 #ifdef __cplusplus
 }
