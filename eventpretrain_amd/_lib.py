@@ -18,6 +18,7 @@ EVP_F32, EVP_BF16 = 0, 1
 CLS_METRICS_SINGLE_ROWS, CLS_METRICS_WS = 1024, 3072      # include/evtpretrain.h EVP_CLS_METRICS_*
 SEMSEG_MAX_CLASSES, SEMSEG_WS_ROW, SEMSEG_SAVED = 32, 100, 68      # include/evtpretrain.h EVP_SEMSEG_*
 FLOW_WS_ROW, FLOW_SAVED = 8, 4      # include/evtpretrain.h EVP_FLOW_*
+RECTIFY_CHUNK_ROWS = 1024      # include/evtpretrain.h EVP_RECTIFY_CHUNK_ROWS: rows per workgroup of evp_events_rectify_compact_f64
 ACT_NONE, ACT_GELU, ACT_DGELU, ACT_RELU, ACT_DRELU = 0, 1, 2, 3, 4
 
 _vp, _i, _i64, _f, _d = C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_double
@@ -145,11 +146,15 @@ SIGNATURES = {
     "evp_flow_objective_fwd": [_vp, _i64, _i, _i, _i, _i, _i, _vp, _vp, _f, _vp, _vp, _vp, _vp],
     "evp_flow_objective_bwd": [_vp, _i64, _i, _i, _i, _i, _i, _vp, _vp, _f, _vp, _vp, _vp, _i64, _vp],
     "evp_flow_metrics": [_vp, _i64, _i, _i, _i, _i, _i, _vp, _vp, _f, _vp, _i, _vp, _vp, _i64, _vp, _vp],
+    "evp_semseg_label_augment": [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp],
+    "evp_flow_label_augment_f32": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp],
+    "evp_events_rectify_compact_ws_words": [_i, _i64],
+    "evp_events_rectify_compact_f64": [_vp, _i64, _vp, _i, _i64, _vp, _i, _i, _i, _i, _i64, _vp, _i64, _vp, _vp, _vp, _vp],
     "evp_abi_version": [],
 }
 _OTHER_RESTYPE = {"evp_last_error": C.c_char_p, "evp_target_arch": C.c_char_p}
-_INT_RESTYPE = {"evp_gemm_stamp_count": C.c_longlong}
-_NO_STATUS = {"evp_dwconv5x5_bwd_nslab", "evp_gemm_set_variant", "evp_voxel_set_debug", "evp_gemm_stamp_count", "evp_attention_fused_supported", "evp_layernorm_bwd_nblk", "evp_colsum_nblk", "evp_batchnorm_nblk", "evp_abi_version", "evp_semseg_nblk", "evp_flow_nblk",
+_INT_RESTYPE = {"evp_gemm_stamp_count": C.c_longlong, "evp_events_rectify_compact_ws_words": C.c_int64}
+_NO_STATUS = {"evp_dwconv5x5_bwd_nslab", "evp_gemm_set_variant", "evp_voxel_set_debug", "evp_gemm_stamp_count", "evp_attention_fused_supported", "evp_layernorm_bwd_nblk", "evp_colsum_nblk", "evp_batchnorm_nblk", "evp_abi_version", "evp_semseg_nblk", "evp_flow_nblk", "evp_events_rectify_compact_ws_words",
               "evp_window_attention_fused_np", "evp_window_attention_fused_nchunk"}
 
 _lib = None

@@ -8,6 +8,8 @@ Here they are explicit, host-drawn int32 rows {x0, y0, w, h, hflip, tflip}:
     `RandomState(seed)` reproduces `evg_augment(..., seed=seed)` bit for bit (pinned by tests/golden/evg_augment.npz);
   * `draw_evg_params_batch(seed, step, B, ...)` -- a counter-based stream (Philox keyed by (seed, step, sample)): the
     decisions of a sample do not depend on worker scheduling or on how many draws other samples consumed.
+The dense fine-tuning labels ride with the grid (view_augment.py:91-134: the reference re-seeds numpy with the sample's seed, so a label gets
+the grid's crop box and flip coins): `semseg_label_augment_batch` and `flow_label_augment_batch` take the same rows (csrc/labels.hip).
 The event-level augmentations (erase / add correlated events) are in events_augment.py next to this file."""
 import math
 
@@ -135,3 +137,59 @@ def frame_augment_batch(frames, params, size, out=None):
         out = torch.empty(B, C, Ho, Wo, dtype=torch.float32, device=frames.device)
     call("evp_frame_augment_f32", ptr(frames), ptr(params), ptr(out), B, C, H, W, Ho, Wo, stream_ptr())
     return out
+
+
+def _label_rows(who, params, B, H, W, device):
+    """The label wrappers' share of evg_augment_batch's params handling: host rows are range-checked and uploaded, device rows taken as they are."""
+    if not torch.is_tensor(params):
+        p = np.ascontiguousarray(params, dtype=np.int32).reshape(B, 6)
+        if ((p[:, 0] < 0) | (p[:, 1] < 0) | (p[:, 2] < 1) | (p[:, 3] < 1) | (p[:, 0] + p[:, 2] > W) | (p[:, 1] + p[:, 3] > H)).any():
+            raise ValueError(f"{who}: crop box outside the view")
+        params = torch.from_numpy(p).to(device, non_blocking=True)
+    if params.dtype != torch.int32 or tuple(params.shape) != (B, 6) or not params.is_contiguous() or not params.is_cuda:
+        raise ValueError(f"{who}: params must be int32 [B,6]")
+    return params
+
+
+def _label_out(who, out, shape, dtype, device):
+    if out is None:
+        return torch.empty(*shape, dtype=dtype, device=device)
+    if tuple(out.shape) != shape or out.dtype != dtype or not out.is_cuda or not out.is_contiguous():
+        raise ValueError(f"{who}: out must be a contiguous {dtype} tensor of shape {shape} in device memory")
+    return out
+
+
+def semseg_label_augment_batch(labels, params, size, out=None):
+    """Segmentation labels of the batch (reference view_augment.py:91-99 `semseg_label_augment`): labels uint8 [B,1,H,W] on the GPU,
+    params int32 [B,6] (host array or device tensor) -- THE SAME rows that went to evg_augment_batch (the reference re-seeds numpy with the
+    sample's seed, so the crop box and the flip coin repeat; column 5, the time flip, does not touch a label) -> int64
+    [B,1,size[0],size[1]]: crop, nearest resize, horizontal flip; equal to the reference's function (tests/golden/dense_label_views.npz)."""
+    who = "semseg_label_augment_batch"
+    _lib.require_device()
+    if not labels.is_cuda or labels.dtype != torch.uint8 or labels.dim() != 4 or labels.shape[1] != 1 or not labels.is_contiguous():
+        raise _lib.EvpError(f"{who}: labels must be a contiguous uint8 [B,1,H,W] tensor in device memory")
+    B, _, H, W = labels.shape
+    params = _label_rows(who, params, B, H, W, labels.device)
+    Ho, Wo = int(size[0]), int(size[1])
+    out = _label_out(who, out, (B, 1, Ho, Wo), torch.int64, labels.device)
+    call("evp_semseg_label_augment", ptr(labels), ptr(params), ptr(out), B, H, W, Ho, Wo, stream_ptr())
+    return out
+
+
+def flow_label_augment_batch(flow, params, size, out=None, valid_out=None):
+    """Flow labels of the batch and their valid mask in one pass (reference view_augment.py:101-134 `flow_label_augment` with evg_augment's
+    time-flip flag, `flow_label_valid_augment` of the dataset's `norm > 0 & |flow| < 1000` mask): flow float32 [B,2,H,W] on the GPU, params
+    int32 [B,6] as semseg_label_augment_batch takes them (column 5 = the time-flip flag: both components change sign) -> (float32
+    [B,2,size[0],size[1]] scaled by (size[1] / w, size[0] / h) of the crop box, float32 [B,1,size[0],size[1]] of 1.0 / 0.0); equal to the
+    reference's functions (tests/golden/dense_label_views.npz)."""
+    who = "flow_label_augment_batch"
+    _lib.require_device()
+    if not flow.is_cuda or flow.dtype != torch.float32 or flow.dim() != 4 or flow.shape[1] != 2 or not flow.is_contiguous():
+        raise _lib.EvpError(f"{who}: flow must be a contiguous float32 [B,2,H,W] tensor in device memory")
+    B, _, H, W = flow.shape
+    params = _label_rows(who, params, B, H, W, flow.device)
+    Ho, Wo = int(size[0]), int(size[1])
+    out = _label_out(who, out, (B, 2, Ho, Wo), torch.float32, flow.device)
+    valid_out = _label_out(who, valid_out, (B, 1, Ho, Wo), torch.float32, flow.device)
+    call("evp_flow_label_augment_f32", ptr(flow), ptr(params), ptr(out), ptr(valid_out), B, H, W, Ho, Wo, stream_ptr())
+    return out, valid_out

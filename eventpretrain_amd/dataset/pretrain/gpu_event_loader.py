@@ -16,7 +16,8 @@ s0 = (w0 * (n - fix)) >> 32, uniform over the WHOLE clip as get_random_index dra
 takes whole, and draws the same counts and crop boxes it would have drawn for the uncut clip.
 
 The pack / upload half (ClipWindowLoader) is shared with dataset.finetune_cls.gpu_event_loader.GpuFinetuneLoader, whose samples carry a
-label in the frame's place."""
+label in the frame's place, and with dataset.finetune_dense.gpu_dense_loader.GpuDenseLoader, whose samples carry a label MAP and whose
+window is the clip's tail (`_window_start`)."""
 from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
@@ -71,6 +72,11 @@ class ClipWindowLoader:
     def _check_window(self, window, name):
         pass
 
+    def _window_start(self, n, fix, w0):
+        """First row of the window of `fix` rows in a clip of `n`: the plan kernel's rule on word 0 of the sample's counter stream, uniform
+        over the whole clip as get_random_index draws it. (The dense loaders take the clip's tail instead.)"""
+        return (w0 * (n - fix)) >> 32 if n > fix else 0
+
     def _pack(self, it, slot, step):
         """Host half of one batch (worker thread): B samples -> their windows in the pinned slot. `step`: the counter stream's step of
         THIS batch (the pack runs one batch ahead). -> (rows, names) or None at the end of the pass."""
@@ -89,7 +95,7 @@ class ClipWindowLoader:
             e = np.asarray(events, dtype=np.float64)
             if e.ndim != 2 or e.shape[1] != 4:
                 raise ValueError(f"{type(self).__name__}: events must be float64 [n,4] (x,y,t,p)")
-            s0 = (int(w0[i]) * (e.shape[0] - fix)) >> 32 if e.shape[0] > fix else 0
+            s0 = self._window_start(e.shape[0], fix, int(w0[i]))
             k = min(e.shape[0], fix)
             self._check_window(e[s0:s0 + k], name)
             ev_h[n:n + k] = e[s0:s0 + k]

@@ -447,6 +447,9 @@ class CapturedChain:
         self.n_tab = 5 * (n_clips + 1) + pw + (pw if frames is not None else 0)
         self.h_tab = torch.zeros(self.n_tab + 2, dtype=torch.int64).pin_memory()      # what the graph's upload node reads (prepared form)
         self.d_tab = torch.zeros(self.n_tab + 2, dtype=torch.int64, device=dev)
+        # the grids' crop rows {x0, y0, w, h, hflip, tflip} of the last replay where they lie in the table (int32 [n_clips,6], a view): what
+        # _launches hands to the view stage as p_dev, and what a label of the same sample is augmented under (view_augment.py:91-134)
+        self.crop_rows = self.d_tab[5 * (n_clips + 1):5 * (n_clips + 1) + pw].view(torch.int32)[:n_clips * 6].view(n_clips, 6)
         self.er = torch.zeros(n_clips * self.kmax, dtype=torch.int64, device=dev)
         self.ai = torch.zeros(n_clips * self.kmax, dtype=torch.int64, device=dev)
         self.nz = torch.zeros(n_clips * self.kmax * 3, dtype=torch.float64, device=dev)

@@ -32,7 +32,8 @@ enum { EVP_ACT_NONE = 0, EVP_ACT_GELU = 1, EVP_ACT_DGELU = 2, EVP_ACT_RELU = 3, 
 const char *evp_last_error(void);
 /* ABI version of this header; bumped on any signature change (2: evp_dropout_fwd takes a device-side seed; evp_gemm_desc lost its
  * stream-K workspace fields in round 3; 3: evp_events_draw_erase_add; 4: keep flags on the window attention; 5: evp_events_plan_batch; entries ADDED since -- evp_cls_metrics,
- * evp_view_augment_bilinear_f32, evp_voxel_scatter_fused_algo_f32, evp_events_window_geometry, evp_events_build_added_hw_f64, evp_semseg_*, evp_flow_* -- change no signature and keep 5). A host binding must compare evp_abi_version() with EVP_ABI_VERSION at load time. */
+ * evp_view_augment_bilinear_f32, evp_voxel_scatter_fused_algo_f32, evp_events_window_geometry, evp_events_build_added_hw_f64, evp_semseg_*, evp_flow_*, evp_semseg_label_augment,
+ * evp_flow_label_augment_f32, evp_events_rectify_compact_f64, evp_events_rectify_compact_ws_words -- change no signature and keep 5). A host binding must compare evp_abi_version() with EVP_ABI_VERSION at load time. */
 #define EVP_ABI_VERSION 5
 int evp_abi_version(void);
 /* Name of the code object's target ("gfx950"). */
@@ -709,6 +710,54 @@ int evp_flow_objective_bwd(const float *map, int64_t ld, int B, int h, int w, in
 int evp_flow_metrics(const float *map, int64_t ld, int B, int h, int w, int H, int W, const float *target, const float *valid,
                      float max_flow, const float *org, int org_channels, int64_t *cursor, float *table, int64_t capacity, void *workspace,
                      void *stream);
+
+/* ------------------------------------------------------------------------------------------------ K29 dense labels and event rectification
+ * The label's share of the dense fine-tuning datasets' view augmentation (dataset/augmentation/view_augment.py:91-134): the reference
+ * re-seeds numpy with the sample's seed before evg_augment, semseg_label_augment, flow_label_augment and flow_label_valid_augment, so the
+ * label gets the grid's crop box and horizontal-flip coin -- here the SAME params rows {x0, y0, w, h, hflip, tflip} (int32 [B,6], device)
+ * the grid's view kernel read, a box with 0 <= x0, x0 + w <= Win, 0 <= y0, y0 + h <= Hin being the caller's to guarantee. Crop ->
+ * F.interpolate(mode='nearest') to Hout x Wout -> horizontal flip of the resized view, by evp_view_augment_f32's index rule
+ *   src = min((int)floorf((float)dst * ((float)in / (float)out)), in - 1)      in = the crop's extent.
+ * evp_semseg_label_augment: labels uint8 [B,1,Hin,Win] -> out int64 [B,1,Hout,Wout] (:91-99; the reference's .float() ... .long() round
+ *   trip is the identity on values <= 255, so the kernel works in integers); tflip is ignored. The full-box row at equal size only widens.
+ * evp_flow_label_augment_f32: flow float32 [B,2,Hin,Win] -> flow_out float32 [B,2,Hout,Wout] and valid_out float32 [B,1,Hout,Wout] in
+ *   one pass (:101-134). With (fx, fy) the nearest source pixel: flow_out = (fx * sxw, fy * syh), sxw = (float)((double)Wout / (double)w),
+ *   syh = (float)((double)Hout / (double)h) (the quotients in double, rounded once, the products in float32, as `flow * torch.tensor([new_w /
+ *   org_w, new_h / org_h])` does); x times -1 on hflip, both components times -1 on tflip (params[5] = evg_augment's time-flip flag).
+ *   valid_out = (fx * fx + fy * fy > 0 && |fx| < 1000 && |fy| < 1000) as 1.0f / 0.0f, on the SOURCE pixel before scaling, the squares and
+ *   the sum rounded separately: the dataset's `torch.norm(flow, dim=0) > 0 & |flow| < 1000` mask (ft_mvsec_dataset.py) under
+ *   flow_label_valid_augment -- a nearest gather of a pointwise mask is the pointwise mask of the gathered pixel. The `> 0` test is pinned
+ *   for exact zeros and for magnitudes >= 1e-6 only: flows whose squares underflow float32 are outside what is pinned.
+ * Both are equal to the reference's functions bit for bit (tests/golden/dense_label_views.npz). */
+int evp_semseg_label_augment(const uint8_t *labels, const int32_t *params, int64_t *out, int B, int Hin, int Win, int Hout, int Wout,
+                             void *stream);
+int evp_flow_label_augment_f32(const float *flow, const int32_t *params, float *flow_out, float *valid_out, int B, int Hin, int Win,
+                               int Hout, int Wout, void *stream);
+/* DSEC's event rectification (dataset/finetune_semseg/ft_dsec_dataset.py:211-226) and DDD17's crop mask with the tail cut behind it
+ * (ft_ddd17_dataset.py:116-127) for a batch of clips: a gather through the rectify map and a STABLE compaction per clip.
+ * events_in float64 [n_rows_in,4] (x,y,t,p), clip c = rows [offsets_in[c], offsets_in[c+1]) (device int64 [n_clips + 1]; at most
+ * max_rows_per_clip rows each -- the launch grid is sized by it). For a row of clip c:
+ *   map (optional, float32 [map_h, map_w, 2]):  (xr, yr) = map[(int)y][(int)x][0..1] widened to double;  NULL: (xr, yr) = (x, y);
+ *   a row whose (int)x, (int)y names no cell of the map (a NaN included) is dropped and counted in status[1] (the reference asserts);
+ *   the row stays iff xr >= 0 && xr < W && yr >= 0 && yr < H -- a NaN drops, -0.0 stays, xr == W drops -- and leaves as (xr, yr, t, p).
+ * Of clip c's T_c survivors the LAST keep_last are written, in their order: events_out rows [offsets_out[c], offsets_out[c+1]) with
+ * offsets_out[0] = 0 and offsets_out[c+1] - offsets_out[c] = min(T_c, keep_last); rows of events_out past offsets_out[n_clips] are not
+ * touched, and no row at or past out_rows is ever written (min(n_rows_in, n_clips * keep_last) rows always suffice).
+ * status (device int32 [2], accumulated: the caller zeroes it): [0] += clips without a survivor; [1] += rows outside the map, and +1
+ * per clip whose offsets are negative, descend, leave events_in or hold more than max_rows_per_clip rows (the excess is not read).
+ * DSEC: the map and keep_last = fix_events_num on tails the host has already cut (the reference cuts before it rectifies); DDD17: map =
+ * NULL on the last fix_events_num + margin rows and keep_last = fix_events_num (the reference masks first and cuts second).
+ * Three launches, no atomic decides a row's place: counts (a ballot and popcount per 64 rows, a chunk of EVP_RECTIFY_CHUNK_ROWS rows per
+ * workgroup) -> one workgroup scans the n_clips * ceil(max_rows_per_clip / EVP_RECTIFY_CHUNK_ROWS) counts and writes offsets_out ->
+ * scatter (row of rank r to offsets_out[c] + r - max(T_c - keep_last, 0); a row is two adjacent 16-byte stores, lanes that keep
+ * neighbouring rows store neighbouring rows). workspace: int32 [evp_events_rectify_compact_ws_words(n_clips, max_rows_per_clip)].
+ * n_clips * max_rows_per_clip (rounded up to chunks) must stay below 2^31. Not in place. */
+#define EVP_RECTIFY_CHUNK_ROWS 1024
+int64_t evp_events_rectify_compact_ws_words(int n_clips, int64_t max_rows_per_clip);
+int evp_events_rectify_compact_f64(const double *events_in, int64_t n_rows_in, const int64_t *offsets_in, int n_clips,
+                                   int64_t max_rows_per_clip, const float *map, int map_h, int map_w, int H, int W, int64_t keep_last,
+                                   double *events_out, int64_t out_rows, int64_t *offsets_out, int32_t *status, int32_t *workspace,
+                                   void *stream);
 
 #ifdef __cplusplus
 }
