@@ -150,6 +150,9 @@ SIGNATURES = {
     "evp_flow_label_augment_f32": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp],
     "evp_events_rectify_compact_ws_words": [_i, _i64],
     "evp_events_rectify_compact_f64": [_vp, _i64, _vp, _i, _i64, _vp, _i, _i, _i, _i, _i64, _vp, _i64, _vp, _vp, _vp, _vp],
+    "evp_event_image_count": [_vp, _i64, _vp, _i, _i64, _i, _i, _d, _d, _vp, _vp, _vp, _vp],
+    "evp_event_image_finish": [_vp, _vp, _i, _i, _i, _i, _vp, _vp],
+    "evp_event_image_normalize": [_vp, _i, _i, _i, _i, _i, _vp, _vp],
     "evp_abi_version": [],
 }
 _OTHER_RESTYPE = {"evp_last_error": C.c_char_p, "evp_target_arch": C.c_char_p}

@@ -42,12 +42,23 @@ Labels travel with the windows: packed into the pinned slot, uploaded into a per
 step, which is queued after this loader yields -- so the event the next upload waits for is recorded on the consumer's stream after
 the generator resumes, behind that step, not behind the chain replay.
 
-Out of scope (NotImplementedError): EvRepSL, the 2- and 3-bin representations. The
+Event-count images (args.num_bins 2 or 3; finetune_recipe gives each dataset's grid, `rescale` and `norm_guard`): the representation
+stage is dataset_utils.events_to_image.event_image_batch (csrc/evimage.hip) in K1's place -- events_to_image_ecdp, or
+events_to_image_mem, / 255 and remove_hot_pixel_mem -- and the datasets' normalisation (per-channel ((v / (max + 1)) - 0.5) * 2, or planes
+0 and 2 over their common max) follows the view stage. Train and noisy validation replay the captured chain in its merged-clip form
+(evp_events_erase_add_win_f64 -> count -> finish -> view -> normalise), clean validation counts the uploaded windows directly. The
+counts are integer sums, so every pass repeats bit for bit. A row whose linear cell index leaves the grid is where the reference
+raises: the device counts such rows and the loader raises ValueError at the end of the pass; `loader.empty_views` is the pass's count
+of all-zero 3-channel views (NaN without the dataset's guard, as in the reference). A time flip reverses the channel order and negates
+nothing (evg_time_flip negates 5- and 6-bin grids only).
+
+Out of scope (NotImplementedError): EvRepSL, event-count images for N-Cars (grid="window"). The
 reference's add_noise_events (events_augment.py) is called by none of its datasets and is not what --val_event_noise means."""
 import numpy as np
 import torch
 
 from ..._lib import call, ptr, stream_ptr
+from ..dataset_utils.events_to_image import event_image_batch
 from ..dataset_utils.events_to_voxel_grid import voxel_grid_batch
 from ..pretrain.gpu_event_loader import ClipWindowLoader
 from ..augmentation.view_augment import evg_augment_batch
@@ -58,17 +69,39 @@ _RECIPES = {"n-imagenet": ("input", "img"), "n-caltech101": ("sensor", "cal"), "
             "dvs128_gesture": ("sensor", "gesture"), "ucf101_dvs": ("sensor", "ucf"), "es-imagenet": ("sensor", "esimg")}
 
 
+# event-count images: dataset_type -> ((grid, rescale) with 2 channels, (grid, rescale) with 3 channels, the `factor = 1.0 / 0.001` guard),
+# read off the reference's files: ft_n_imagenet_dataset.py:92-115 (events_reshape ahead of both branches), ft_n_caltech101_dataset.py:71-98
+# (both at the sensor's size), ft_cifar10_dvs_dataset.py:69-92, ft_dvs128_gesture_dataset.py:73-96 and ft_ucf101_dvs_dataset.py:75-101
+# (events_reshape inside the 2-channel branch only; UCF101-DVS alone has the `else`), ft_es_imagenet_dataset.py:109-131 (2 channels on
+# input_size x input_size with no events_reshape at all; `if max > 0` skips the product, which on an all-zero view is the guard's result)
+_COUNT_RECIPES = {"n-imagenet": (("input", True), ("input", True), False), "n-caltech101": (("sensor", True), ("sensor", True), False),
+                  "cifar10-dvs": (("input", True), ("sensor", True), False), "dvs128_gesture": (("input", True), ("sensor", True), False),
+                  "ucf101_dvs": (("input", True), ("sensor", True), True), "es-imagenet": (("input", False), ("sensor", True), True)}
+
+
 def finetune_recipe(args):
     """-> dict(grid=..., sensor=(h, w)): GpuFinetuneLoader's recipe keywords for args.dataset_type, the sensor read from the reference's
-    own argument names for that dataset (cal_sensor_h / _w for N-Caltech101, ...). The loader never calls this on its own."""
+    own argument names for that dataset (cal_sensor_h / _w for N-Caltech101, ...). The loader never calls this on its own.
+    With args.num_bins in (2, 3) (event-count images) the grid is the one the dataset's own branch for that representation counts on,
+    and two more keywords come along: rescale (False: the events are counted at their sensor coordinates on the S x S grid) and
+    norm_guard (the dataset multiplies an all-zero 3-channel view by 1.0 / 0.001 where the others divide by zero)."""
     kind = args.dataset_type
+    count = int(getattr(args, "num_bins", 5)) in (2, 3)
     if kind == "n-cars":
+        if count:
+            raise NotImplementedError("finetune_recipe: n-cars event-count images (num_bins 2 / 3) are out of scope: its per-clip window grids "
+                                      "(ncars_recipe) are voxel grids only")
         raise NotImplementedError("finetune_recipe: n-cars sizes each grid from the window's own max(x) + 1 and max(y) + 1, so its recipe carries "
                                   "a capacity in the sensor's place: use ncars_recipe(args)")
     if kind not in _RECIPES:
         raise ValueError(f"finetune_recipe: unknown dataset_type {kind!r} (one of {sorted(_RECIPES)})")
     grid, prefix = _RECIPES[kind]
-    return dict(grid=grid, sensor=(int(getattr(args, prefix + "_sensor_h")), int(getattr(args, prefix + "_sensor_w"))))
+    sensor = (int(getattr(args, prefix + "_sensor_h")), int(getattr(args, prefix + "_sensor_w")))
+    if not count:
+        return dict(grid=grid, sensor=sensor)
+    two, three, guard = _COUNT_RECIPES[kind]
+    grid, rescale = two if int(args.num_bins) == 2 else three
+    return dict(grid=grid, sensor=sensor, rescale=rescale, norm_guard=guard)
 
 
 def ncars_recipe(args):
@@ -78,13 +111,16 @@ def ncars_recipe(args):
 
 
 class GpuFinetuneLoader(ClipWindowLoader):
-    def __init__(self, args, samples, batch_size, n_batches, is_train, seed=0, first_sample=0, step0=0, grid="input", sensor=None):
+    def __init__(self, args, samples, batch_size, n_batches, is_train, seed=0, first_sample=0, step0=0, grid="input", sensor=None,
+                 rescale=True, norm_guard=False):
         """`samples`: a re-iterable (one pass per epoch) of (events, label, name); `n_batches`: batches per pass (a short last batch is
         dropped). `step0`: the counter stream's step of the first batch (a training loader continues across epochs, a validation
         loader restarts there). Yields {"events_voxel_grid": float32 [B,bins,S,S], "label": int64 [B], "image_name": [B names]}:
-        device tensors the next batch overwrites. `grid` / `sensor`: the recipe (module docstring), passed to GpuInputPipeline."""
-        if int(args.num_bins) in (2, 3):
-            raise NotImplementedError("GpuFinetuneLoader: the 2- and 3-bin event representations are out of scope (voxel grids only)")
+        device tensors the next batch overwrites. `grid` / `sensor` / `rescale` / `norm_guard`: the recipe (module docstring), passed
+        to GpuInputPipeline; the last two matter for event-count images (args.num_bins 2 or 3) only."""
+        if int(args.num_bins) in (2, 3) and grid == "window":
+            raise NotImplementedError("GpuFinetuneLoader: event-count images (num_bins 2 / 3) on N-Cars' per-clip window grids are out of scope "
+                                      "(voxel grids only)")
         if getattr(args, "use_evrepsl", False):
             raise NotImplementedError("GpuFinetuneLoader: EvRepSL preprocessing is out of scope")
         self.is_train, self.step0 = bool(is_train), int(step0)
@@ -93,11 +129,15 @@ class GpuFinetuneLoader(ClipWindowLoader):
         mode = getattr(args, "resize_mode", "bilinear")
         # (the pipeline validates grid / sensor / mode before any device memory is taken)
         pipe = GpuInputPipeline(args, seed=seed, resize_mode=mode, grid=grid, sensor=sensor, fix_events_num=fix,
-                                view_augment=self.is_train, voxel_cells="f32" if self.is_train else "f64")
+                                view_augment=self.is_train, voxel_cells="f32" if self.is_train else "f64", rescale=rescale,
+                                norm_guard=norm_guard, representation="count" if int(args.num_bins) in (2, 3) else "voxel")
         self._setup(args, samples, batch_size, n_batches, seed, first_sample, step0, fix, fix)
         self.S, self.bins, self.resize_mode = int(args.input_size), int(args.num_bins), mode
         self.sensor, self.grid_hw, self.scale, self.window = pipe.sensor, (pipe.gh, pipe.gw), pipe.scale, pipe.grid == "window"
         self.pipe = self.chain = self.out = self.raw = self.ext = self.geom_status = None
+        # event-count images: the pipeline's device counts {rows outside the grid, all-zero 3-channel views}, read at the end of a pass
+        self.count, self._clean_pipe, self.empty_views = pipe.count, pipe, 0
+        self.image_status = pipe._status(self.dev) if pipe.count else None
         if self.is_train or self.noisy_val:
             self.pipe = pipe
             self.chain = pipe.capture(self.ev, self.B, clip_offsets=np.zeros(self.B + 1, np.int64))
@@ -146,6 +186,16 @@ class GpuFinetuneLoader(ClipWindowLoader):
             raise ValueError(f"GpuFinetuneLoader: evp_events_window_geometry refused {bad} window(s) of this pass (empty, a negative coordinate, "
                              f"or an extent above the capacity {self.sensor[0]} x {self.sensor[1]}); their grids were clamped")
 
+    def _images_checked(self):
+        """End of a pass with event-count images: the two device counts, read once and cleared."""
+        if self.image_status is None:
+            return
+        outside, self.empty_views = (int(v) for v in self.image_status.tolist())
+        self.image_status.zero_()
+        if outside:
+            raise ValueError(f"GpuFinetuneLoader: {outside} event row(s) of this pass fall outside the {self.grid_hw[0]} x {self.grid_hw[1]} grid "
+                             "the images are counted on (the reference's bincount / reshape raises there); they were left out")
+
     def __iter__(self):
         if not self.is_train:
             self.step = self.step0
@@ -161,12 +211,18 @@ class GpuFinetuneLoader(ClipWindowLoader):
                 if self.window:
                     call("evp_events_window_geometry", ptr(self.ev), ptr(self.d_off), ptr(self.d_off[1:]), self.B, self.sensor[0], self.sensor[1], 0,
                          1.0, 0, 0, 0, None, ptr(self.ext), ptr(self._full), ptr(self.geom_status), stream_ptr())
-                vox = voxel_grid_batch(self.ev[:n], self.d_off, self.bins, self.grid_hw, scale=self.scale,
-                                       out=self.out if self.raw is None else self.raw, algo=3)
+                if self.count:
+                    vox = event_image_batch(self.ev[:n], self.d_off, self.bins, self.grid_hw, scale=self.scale,
+                                            out=self.out if self.raw is None else self.raw, status=self.image_status[:1], max_rows_per_clip=self.fix)
+                else:
+                    vox = voxel_grid_batch(self.ev[:n], self.d_off, self.bins, self.grid_hw, scale=self.scale,
+                                           out=self.out if self.raw is None else self.raw, algo=3)
                 if self.raw is not None:
                     vox = evg_augment_batch(vox, self._full, (self.S, self.S), out=self.out, mode=self.resize_mode)
+                self._clean_pipe._tail(vox)
             self.step += 1
             yield {"events_voxel_grid": vox, "label": self._lab[slot], "image_name": names}
             # the consumer has queued its step: what reads the grids, the labels and (before it) the event buffer is on its stream now
             self._mark_read(torch.cuda.current_stream(self.dev))
         self._geometry_checked()
+        self._images_checked()

@@ -43,7 +43,15 @@ view kernels run at, and a kernel of the captured self-driven chain (evp_events_
 on the clip's own grid and hands the extent to the added-row build (evp_events_build_added_hw_f64) -- that chain is the only way to run
 it; `sensor`, `fix_events_num` override the namespace's fields; `view_augment=False` makes the view stage
 view_resize alone (the validation recipe); `voxel_cells="f64"` bins the captured chain's fused K1 with float64 LDS cells
-(evp_voxel_scatter_fused_algo_f32, algo 3), whose grids repeat bit for bit from launch to launch."""
+(evp_voxel_scatter_fused_algo_f32, algo 3), whose grids repeat bit for bit from launch to launch.
+
+Event-count images: with `representation="count"` (args.num_bins 2 or 3; the default "voxel" bins voxel grids at any bin count, the
+pre-training chain's meaning of num_bins) the representation stage is dataset_utils.events_to_image.event_image_batch in the
+voxel grid's place (the classification fine-tuning datasets' events_to_image_ecdp / events_to_image_mem branches), always on the merged
+clip -- a captured chain takes its `fused_voxel=False` form -- and the datasets' normalisation (event_image_normalize_) follows the view
+stage. `rescale=False` counts UNSCALED events on the S x S grid (ES-ImageNet's 2-channel branch), `norm_guard` is the `factor = 1.0 /
+0.001` of the datasets that have it. `image_status` (int32 [2] on the device, accumulated) counts the rows outside the grid and the
+all-zero 3-channel views. grid="window" has no count images (NotImplementedError)."""
 from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
@@ -53,6 +61,7 @@ from ... import _lib
 from ..._lib import call, ptr, stream_ptr
 from ..augmentation import events_augment as ea
 from ..augmentation import view_augment as va
+from ..dataset_utils.events_to_image import event_image_batch, event_image_normalize_
 from ..dataset_utils.events_to_voxel_grid import voxel_grid_batch
 
 
@@ -67,7 +76,8 @@ class PreparedBatch:
 
 class GpuInputPipeline:
     def __init__(self, args, seed=0, decision_stream="device", ring=4, legacy_order="chain", resize_mode="nearest", grid="input", sensor=None,
-                 fix_events_num=None, view_augment=True, voxel_cells="f32"):
+                 fix_events_num=None, view_augment=True, voxel_cells="f32", rescale=True, norm_guard=False,
+                 representation="voxel"):
         """args: the reference's namespace (fix_events_num, img_sensor_h / _w, input_size, num_bins, crop_min). `ring`: pinned slots
         for prepared batches (how many may exist at once before their run_prepared). `resize_mode`: evg_augment's `mode`, "nearest"
         (the pre-training datasets) or "bilinear" (the fine-tuning datasets' default); a keyword of its own, never read from `args`.
@@ -79,7 +89,10 @@ class GpuInputPipeline:
         `sensor`: (h, w) in place of (args.img_sensor_h, args.img_sensor_w). `fix_events_num`: in place of args.fix_events_num (window
         length, bound of the erase / add counts). `view_augment=False`: the view stage is view_resize alone -- the constant row
         (0, 0, W, H, 0, 0) for every clip, and no resize at all where the grid already has the view's size (the validation recipe).
-        `voxel_cells`: the captured chain's fused K1 accumulates in "f32" or "f64" LDS cells (evp_voxel_scatter_fused_algo_f32 algo 0 / 3)."""
+        `voxel_cells`: the captured chain's fused K1 accumulates in "f32" or "f64" LDS cells (evp_voxel_scatter_fused_algo_f32 algo 0 / 3).
+        `rescale=False` (grid="input" only): no events_reshape -- the events are binned on the S x S grid at their sensor coordinates.
+        `norm_guard`: event-count images with 3 channels multiply an all-zero view by 1000 where the reference's dataset does.
+        `representation`: "voxel" (default: voxel grids, whatever num_bins) or "count" (event-count images; num_bins must be 2 or 3)."""
         self.RING = int(ring)
         if grid not in ("input", "sensor", "window"):
             raise ValueError(f"grid must be 'input', 'sensor' or 'window' (got {grid!r})")
@@ -102,11 +115,20 @@ class GpuInputPipeline:
         self.S = int(args.input_size)
         # the grid K1 bins at, and the x / y scale it applies: the input's size after events_reshape, or the sensor's own
         self.gh, self.gw = (self.S, self.S) if grid == "input" else self.sensor
-        self.scale = (self.S / self.sensor[1], self.S / self.sensor[0]) if grid == "input" else (1.0, 1.0)
+        self.scale = (self.S / self.sensor[1], self.S / self.sensor[0]) if grid == "input" and rescale else (1.0, 1.0)
         # is the view stage a real resize? (view_resize of an S x S grid to S x S is the identity; a window grid always differs from its capacity)
         self.resize = self.view_augment or (self.gh, self.gw) != (self.S, self.S) or grid == "window"
         self._full_rows = {}
         self.bins = int(args.num_bins)
+        # event-count images (2 / 3 channels) in the voxel grid's place, the datasets' normalisation behind the view stage
+        if representation not in ("voxel", "count"):
+            raise ValueError(f"representation must be 'voxel' or 'count' (got {representation!r})")
+        if representation == "count" and self.bins not in (2, 3):
+            raise ValueError(f"representation='count' needs num_bins 2 or 3 (got {self.bins}): the reference's datasets have no other count image")
+        self.count, self.norm_guard, self.image_status = representation == "count", bool(norm_guard), None
+        if self.count and grid == "window":
+            raise NotImplementedError("GpuInputPipeline: grid='window' (N-Cars) has no event-count images (num_bins 2 / 3): its per-clip grids "
+                                      "are voxel grids only")
         self.crop_min = float(getattr(args, "crop_min", 0.8))
         self._pins, self._busy, self._turn, self._pool = [None] * self.RING, [None] * self.RING, 0, None
 
@@ -122,6 +144,25 @@ class GpuInputPipeline:
         if key not in self._full_rows:
             self._full_rows[key] = torch.tensor([[0, 0, self.gw, self.gh, 0, 0]] * int(n_clips), dtype=torch.int32, device=device)
         return self._full_rows[key]
+
+    def _status(self, device):
+        """Event-count images: int32 [2] = {rows outside the grid, all-zero 3-channel views}, accumulated on the device."""
+        if self.image_status is None:
+            self.image_status = torch.zeros(2, dtype=torch.int32, device=device)
+        return self.image_status
+
+    def _represent(self, ev, off, max_rows=None, **voxel_kw):
+        """Merged clips -> the raw representation [B, bins, gh, gw]: voxel grids (K1), or event-count images (representation="count")."""
+        if self.count:
+            return event_image_batch(ev, off, self.bins, (self.gh, self.gw), scale=self.scale, status=self._status(ev.device)[:1],
+                                     max_rows_per_clip=max_rows)
+        return voxel_grid_batch(ev, off, self.bins, (self.gh, self.gw), scale=self.scale, **voxel_kw)
+
+    def _tail(self, views):
+        """What follows the view stage: nothing for voxel grids, the datasets' normalisation for event-count images (in place)."""
+        if self.count:
+            event_image_normalize_(views, guard=self.norm_guard, status=self._status(views.device)[1:])
+        return views
 
     def _view(self, vox, p_dev, out=None):
         """Grids [B, bins, gh, gw] -> views [B, bins, S, S]: evg_augment under the drawn rows, or view_resize alone (the identity, and no
@@ -214,7 +255,7 @@ class GpuInputPipeline:
             raise ValueError("GpuInputPipeline.run takes per-clip decision lists; with decision_stream='device' use prepare() / run_prepared() "
                              "(or batch()), or read the device's draws back with device_decisions()")
         ev, off = ea.events_augment_batch(events, clip_offsets, decisions, (H, W), windows=windows)
-        vox = voxel_grid_batch(ev, off, self.bins, (self.gh, self.gw), assume_sorted=assume_sorted, scale=self.scale)
+        vox = self._represent(ev, off, assume_sorted=assume_sorted)
         # the grid's and the frames' parameter rows in ONE upload (each pageable copy is a stall of the host)
         both = frames is not None and frame_params is not None and not torch.is_tensor(frame_params)
         rows = np.ascontiguousarray(params, dtype=np.int32).reshape(-1, 6)
@@ -226,7 +267,7 @@ class GpuInputPipeline:
             rows = np.concatenate([rows, fr], 0)
         p_all = torch.from_numpy(rows).to(events.device, non_blocking=True)
         p_dev = p_all[:len(params)]
-        out = self._view(vox, p_dev)
+        out = self._tail(self._view(vox, p_dev))
         tgt = None
         if frames is not None:
             fp = p_all[len(params):] if both else (p_dev if frame_params is None else frame_params)
@@ -342,9 +383,9 @@ class GpuInputPipeline:
             er_d, ai_d, nz_d = d[o[0]:o[1]], d[o[1]:o[2]], d[o[2]:o[3]]
         call("evp_events_erase_add_win_f64", ptr(events), ptr(tabs[0]), ptr(tabs[1]), nc, ptr(er_d), ptr(tabs[2]), ptr(ai_d),
              ptr(nz_d), ptr(tabs[3]), pb.max_add, float(W), float(H), ptr(ws), ptr(tabs[4]), ptr(ev), stream_ptr())
-        vox = voxel_grid_batch(ev, tabs[4], self.bins, (self.gh, self.gw), assume_sorted=assume_sorted, scale=self.scale)
+        vox = self._represent(ev, tabs[4], assume_sorted=assume_sorted)
         p_dev = d[o[4]:o[5]].view(torch.int32)[:nc * 6].view(nc, 6)
-        out = self._view(vox, p_dev)
+        out = self._tail(self._view(vox, p_dev))
         tgt = None
         if frames is not None:
             fp = d[o[5]:o[6]].view(torch.int32)[:nc * 6].view(nc, 6) if pb.fparams is not None else p_dev
@@ -454,7 +495,9 @@ class CapturedChain:
         self.ai = torch.zeros(n_clips * self.kmax, dtype=torch.int64, device=dev)
         self.nz = torch.zeros(n_clips * self.kmax * 3, dtype=torch.float64, device=dev)
         self.ws = torch.zeros(n_clips * self.kmax, 4, dtype=torch.float64, device=dev)
-        self.fused = bool(fused_voxel) and fix <= 48 * 1024 * 8
+        # (event-count images are counted on the merged clip: the fused K1 bins voxel grids)
+        self.fused = bool(fused_voxel) and fix <= 48 * 1024 * 8 and not pipe.count
+        self.image_status = pipe._status(dev) if pipe.count else None
         if self.window and not self.fused:
             raise ValueError(f"CapturedChain: grid='window' runs in the captured self-driven chain's fused form only (fix_events_num {fix} is too long for it)")
         self.ev = None if self.fused else torch.zeros(n_clips * (fix + self.kmax), 4, dtype=torch.float64, device=dev)
@@ -499,6 +542,8 @@ class CapturedChain:
             self.set_state(0, 0)                      # the warm-up advanced it
         if self.window:
             self.geom_status.zero_()                  # (a warm-up on offsets that are still zero counts B empty windows)
+        if self.image_status is not None:
+            self.image_status.zero_()                 # (likewise: B all-zero views)
 
     def set_clip_offsets(self, clip_offsets):
         """Self-driven chain: the clip offsets of the rows now in the event buffer (int64 [n_clips + 1], host or device). Every clip's
@@ -576,10 +621,9 @@ class CapturedChain:
         else:
             call("evp_events_erase_add_win_f64", ptr(self.events), ptr(tabs[0]), ptr(tabs[1]), nc, ptr(self.er), ptr(tabs[2]), ptr(self.ai),
                  ptr(self.nz), ptr(tabs[3]), self.kmax, float(W), float(H), ptr(self.ws), ptr(tabs[4]), ptr(self.ev), stream_ptr())
-            vox = voxel_grid_batch(self.ev, tabs[4], pipe.bins, (pipe.gh, pipe.gw), assume_sorted=True, scale=pipe.scale,
-                                   algo=self.algo)
+            vox = pipe._represent(self.ev, tabs[4], max_rows=self.fix + self.kmax, assume_sorted=True, algo=self.algo)
             p_dev = d[o4:o4 + pw].view(torch.int32)[:nc * 6].view(nc, 6)
-            out = pipe._view(vox, p_dev, out=self._out_given)
+            out = pipe._tail(pipe._view(vox, p_dev, out=self._out_given))
         tgt = None
         if fr is not None:
             # (as a parallel branch of the graph the frame targets cost more than they hide: 408 vs 389 us per batch with fork + join)

@@ -759,6 +759,35 @@ int evp_events_rectify_compact_f64(const double *events_in, int64_t n_rows_in, c
                                    double *events_out, int64_t out_rows, int64_t *offsets_out, int32_t *status, int32_t *workspace,
                                    void *stream);
 
+/* ------------------------------------------------------------------------------------------------ K30 event-count images
+ * The 2- and 3-channel representations of the classification fine-tuning datasets (dataset/dataset_utils/events_to_image.py as every
+ * dataset/finetune_cls/ file calls it with num_bins 2 and 3), in three stages around the view kernels (K22), which take any channel count.
+ * evp_event_image_count: events float64 [n_rows,4] (x,y,t,p), clip c = rows [clip_offsets[c], clip_offsets[c+1]) clamped to [0, n_rows)
+ *   (device int64 [n_clips + 1]; max_rows_per_clip only sizes the launch grid) -> planes int32 [n_clips,3,H,W] counting the rows with
+ *   p == 1, p == 0 and p == -1, zero_rows int32 [n_clips] = the clip's count of p == 0 rows; both are cleared by the call (a kernel, so
+ *   inside a captured graph too). Cell of a row: lin = (int64)(x * sx) + (int64)(y * sy) * W, the products in float64 as events_reshape
+ *   (events_augment.py:22-26) leaves them, the conversions truncating toward zero as .long() does; the row is counted when
+ *   0 <= lin < H * W, so x >= W wraps into the next row as torch.bincount on the linear index has it. Any other lin (a NaN, a magnitude
+ *   beyond int64 included) is not counted and adds 1 to status[0] (device int32, accumulated: the caller zeroes it) -- the reference
+ *   raises there. Rows of any other polarity are ignored. Global int32 atomics only: every result is an integer sum, equal from launch to
+ *   launch bit for bit.
+ * evp_event_image_finish: -> out float32 [n_clips,C,H,W]. neg = the p == 0 plane of a clip with zero_rows > 0, else its p == -1 plane
+ *   (the reference's `if len(neg_events) == 0`, per clip). C = 2 (events_to_image_ecdp): {pos, neg} as floats. C = 3 (events_to_image_mem,
+ *   / 255, remove_hot_pixel_mem): {pos / 255, 0, neg / 255} in float32, then with S1 = sum k and S2 = sum k^2 over the n = 2 H W counts of
+ *   planes 0 and 2 as exact integers and, in float64, mean = S1 / n / 255, var = (S2 - S1 * S1 / n) / (n - 1) / 255^2,
+ *   thr = mean + 10 sqrt(max(var, 0)): a pixel of either plane with (double)value > thr zeroes both planes at that (row, col). The
+ *   reference takes mean and std in float32 in ATen's summation order; the two can differ only for a value within rounding of thr.
+ * evp_event_image_normalize: views float32 [n_views,C,H,W] in place, after the view stage. C = 2: per channel m = max of the plane,
+ *   v = ((v / (m + 1)) - 0.5) * 2, each operation one correctly rounded float32 operation: torch's bits. C = 3: m = max over planes 0 and 2,
+ *   both times 1.0f / m, plane 1 untouched; a view with m == 0 adds 1 to status[0] (device int32, accumulated) and is multiplied by 1000.0f
+ *   when `guard` is set (ft_ucf101_dvs_dataset.py:97-101 `factor = 1.0 / 0.001`; ft_es_imagenet_dataset.py:129 skips the product, which
+ *   is the same on an all-zero view), by 1.0f / 0.0f otherwise: 0 * inf = NaN, the reference's result. Views are assumed free of NaN.
+ *   status is not touched for C = 2. H * W <= 2^26, n_clips and n_views <= 65535. */
+int evp_event_image_count(const double *events, int64_t n_rows, const int64_t *clip_offsets, int n_clips, int64_t max_rows_per_clip, int H,
+                          int W, double sx, double sy, int32_t *planes, int32_t *zero_rows, int32_t *status, void *stream);
+int evp_event_image_finish(const int32_t *planes, const int32_t *zero_rows, int n_clips, int C, int H, int W, float *out, void *stream);
+int evp_event_image_normalize(float *views, int n_views, int C, int H, int W, int guard, int32_t *status, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
