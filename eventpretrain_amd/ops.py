@@ -1126,12 +1126,18 @@ class RecLossFn(torch.autograd.Function):
              ptr(_chk(target.detach().contiguous(), torch.float32)), ptr(mask), B, Cc, H, W, patch, int(bool(norm_pix)),
              ptr(loss), ptr(dpred), ptr(ws), stream_ptr())
         ctx.save_for_backward(dpred)
+        ctx.scaled = False
         return loss.view(())
 
     @staticmethod
     def backward(ctx, g):
         (dpred,) = ctx.saved_tensors
-        # upstream gradient is a device scalar (1, or 1/accum_iter): scale in place without a host sync
+        # upstream gradient is a device scalar (1, or 1/accum_iter): scale in place without a host sync. The saved gradient is
+        # consumed by that: a second pass through the same forward (retain_graph=True) would return g * g' * dpred, so it is refused
+        if ctx.scaled:
+            raise _lib.EvpError("RecLossFn: backward ran twice through one forward; the saved gradient is scaled in place by the "
+                                "upstream scalar and cannot be used again -- run the forward again")
+        ctx.scaled = True
         call("evp_scale_f32", ptr(dpred), ptr(_chk(g.contiguous().view(1), torch.float32)), dpred.numel(), stream_ptr())
         return dpred, None, None, None, None
 
