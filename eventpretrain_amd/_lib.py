@@ -15,6 +15,7 @@ CSRC = os.path.join(_HERE, "csrc")
 
 ABI_VERSION = 5            # include/evtpretrain.h EVP_ABI_VERSION: checked when the library is loaded (EVP_LIB overrides included)
 EVP_F32, EVP_BF16 = 0, 1
+EVP_F64 = 2                # float64 frames of evp_mvsec_flow_propagate, the one entry that takes it
 CLS_METRICS_SINGLE_ROWS, CLS_METRICS_WS = 1024, 3072      # include/evtpretrain.h EVP_CLS_METRICS_*
 SEMSEG_MAX_CLASSES, SEMSEG_WS_ROW, SEMSEG_SAVED = 32, 100, 68      # include/evtpretrain.h EVP_SEMSEG_*
 FLOW_WS_ROW, FLOW_SAVED = 8, 4      # include/evtpretrain.h EVP_FLOW_*
@@ -150,6 +151,7 @@ SIGNATURES = {
     "evp_flow_label_augment_f32": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp],
     "evp_events_rectify_compact_ws_words": [_i, _i64],
     "evp_events_rectify_compact_f64": [_vp, _i64, _vp, _i, _i64, _vp, _i, _i, _i, _i, _i64, _vp, _i64, _vp, _vp, _vp, _vp],
+    "evp_mvsec_flow_propagate": [_vp, _i, _i64, _i, _i, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp],
     "evp_event_image_count": [_vp, _i64, _vp, _i, _i64, _i, _i, _d, _d, _vp, _vp, _vp, _vp],
     "evp_event_image_finish": [_vp, _vp, _i, _i, _i, _i, _vp, _vp],
     "evp_event_image_normalize": [_vp, _i, _i, _i, _i, _i, _vp, _vp],

@@ -4,7 +4,9 @@
 //     re-seed numpy with the sample's seed, so the label gets the grid's crop box and horizontal-flip coin: one gather per output pixel
 //     under the SAME int32 [B,6] crop rows the grid's view kernel read (csrc/augment.hip), wherever they lie in device memory;
 //   * DSEC's event rectification (dataset/finetune_semseg/ft_dsec_dataset.py:211-226) and DDD17's crop mask with the tail cut behind it
-//     (ft_ddd17_dataset.py:116-127): a gather through the rectify map and a STABLE stream compaction per clip.
+//     (ft_ddd17_dataset.py:116-127): a gather through the rectify map and a STABLE stream compaction per clip;
+//   * MVSEC's flow label itself (dataset/finetune_flow/ft_mvsec_dataset.py:121-188): the pixel grid propagated through the resident
+//     ground-truth flow frames, a handful of gathers per output pixel.
 // All of it is HBM-bound: the label views write coalesced rows (8 B per pixel for the int64 label, 12 B for flow + valid) and gather 1 /
 // 8 B; the compaction reads every row once per pass (32 B + 8 B of map) and writes the survivors as whole 32-byte rows, neighbouring
 // survivors to neighbouring rows. No atomic orders anything: ranks come from wave ballots, an LDS exchange and a scan of chunk counts.
@@ -90,6 +92,98 @@ extern "C" int evp_flow_label_augment_f32(const float *flow, const int32_t *para
   hipLaunchKernelGGL(flow_label_augment_kernel, grid, dim3(256), 0, (hipStream_t)stream, flow, params, flow_out, valid_out, Hin, Win, Hout,
                      Wout);
   EVP_CHECK_LAUNCH("evp_flow_label_augment_f32");
+  return EVP_OK;
+}
+
+// ---- MVSEC's ground-truth flow label: propagate a pixel grid through the flow frames ---------------------------------------------
+// gen_correspond_gt_flow (dataset/finetune_flow/ft_mvsec_dataset.py:121-188) per output pixel: the frames of every sequence stay in
+// device memory, a sample is a row of hops (frame index, float64 scale) the host made from two timestamps. A thread carries x, y and the
+// two flags in registers; a hop is two 4- or 8-byte gathers at the rounded position (neighbouring pixels mostly read neighbouring cells),
+// the two planes leave as coalesced rows. Floor: 8 B (float32 frames) gathered per hop and pixel + 8 B written.
+//
+// cv2.remap(..., INTER_NEAREST) picks its cell with cvRound: round half to EVEN, the border a constant 0. That rule is stated from
+// OpenCV's source and has NOT been checked against a real cv2 (tests/golden/mvsec_gt_flow.npz was made with a stand-in that states the
+// same rule); it lives in this one function, so a correction is one line.
+__device__ __forceinline__ float remap_nearest_round(float v) { return rintf(v); }
+
+// frame's two planes at the cell (x, y) rounds to; outside the frame, and for a NaN (which fails every comparison): 0
+template <typename T>
+__device__ __forceinline__ void gt_flow_fetch(const T *__restrict__ frame, int H, int W, float x, float y, double &ax, double &ay) {
+  const float rx = remap_nearest_round(x), ry = remap_nearest_round(y);
+  ax = ay = 0.0;
+  if (rx >= 0.0f && rx < (float)W && ry >= 0.0f && ry < (float)H) {       // (-0.0 names column 0)
+    const int64_t cell = (int64_t)(int)ry * W + (int)rx;
+    ax = (double)frame[cell];
+    ay = (double)frame[(int64_t)H * W + cell];
+  }
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void mvsec_flow_propagate_kernel(const T *__restrict__ frames, int64_t n_frames, int H, int W,
+                                                                   const int64_t *__restrict__ hop_frame,
+                                                                   const double *__restrict__ hop_scale, const int32_t *__restrict__ n_hops,
+                                                                   int max_hops, float *__restrict__ out, int32_t *__restrict__ status) {
+  const int b = blockIdx.y;
+  const int n = n_hops[b];
+  const int64_t *hf = hop_frame + (int64_t)b * max_hops;
+  const double *hs = hop_scale + (int64_t)b * max_hops;
+  // the sample's table, checked by every thread alike (uniform: no divergence): a row that names no frame is never followed
+  bool bad = n < 0 || n > max_hops;
+  if (!bad) {
+    const int rows = n == 0 ? 1 : n;                                      // the direct branch reads row 0
+    for (int k = 0; k < rows; ++k) bad |= hf[k] < 0 || hf[k] >= n_frames;
+  }
+  if (bad) {
+    if (blockIdx.x == 0 && threadIdx.x == 0) atomicAdd(status, 1);        // a counter, not an order
+    return;
+  }
+  const int64_t plane = (int64_t)H * W;
+  const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (p >= plane) return;
+  float *ox = out + (int64_t)b * 2 * plane + p, *oy = ox + plane;
+  if (n == 0) {
+    // x_flow *= pre_dt / gt_dt: the product in float64, rounded once into the frame's dtype (then, a float64 frame, into the label's)
+    const T *frame = frames + hf[0] * 2 * plane;
+    const double s = hs[0];
+    *ox = (float)(T)__dmul_rn((double)frame[p], s);
+    *oy = (float)(T)__dmul_rn((double)frame[plane + p], s);
+    return;
+  }
+  const int row = (int)(p / W), col = (int)(p - (int64_t)row * W);
+  float x = (float)col, y = (float)row;
+  bool x_ok = true, y_ok = true;
+  for (int k = 0; k < n; ++k) {
+    const double s = hs[k];
+    double ax, ay;
+    gt_flow_fetch(frames + hf[k] * 2 * plane, H, W, x, y, ax, ay);        // both planes at the position BEFORE the update
+    x_ok &= ax != 0.0;
+    y_ok &= ay != 0.0;
+    // x_indices += flow_x_interp * scale_factor: product and sum each rounded to float64, then once to float32 -- never an FMA
+    x = (float)__dadd_rn((double)x, __dmul_rn(ax, s));
+    y = (float)__dadd_rn((double)y, __dmul_rn(ay, s));
+  }
+  *ox = x_ok ? __fsub_rn(x, (float)col) : 0.0f;
+  *oy = y_ok ? __fsub_rn(y, (float)row) : 0.0f;
+}
+
+extern "C" int evp_mvsec_flow_propagate(const void *frames, int frames_dtype, int64_t n_frames, int H, int W, const int64_t *hop_frame,
+                                        const double *hop_scale, const int32_t *n_hops, int B, int max_hops, float *label_out,
+                                        int32_t *status, void *stream) {
+  EVP_CHECK_ARG(frames && hop_frame && hop_scale && n_hops && label_out && status, EVP_EINVAL, "evp_mvsec_flow_propagate: null pointer");
+  EVP_CHECK_ARG(frames_dtype == EVP_F32 || frames_dtype == EVP_F64, EVP_EINVAL,
+                "evp_mvsec_flow_propagate: frames_dtype %d (EVP_F32 or EVP_F64)", frames_dtype);
+  EVP_CHECK_ARG((((uintptr_t)frames) & (frames_dtype == EVP_F64 ? 7 : 3)) == 0 && (((uintptr_t)hop_frame | (uintptr_t)hop_scale) & 7) == 0,
+                EVP_EINVAL, "evp_mvsec_flow_propagate: frames, hop_frame and hop_scale must be aligned to their elements");
+  EVP_CHECK_ARG(n_frames > 0 && H > 0 && W > 0 && B > 0 && B <= 65535 && max_hops > 0 && (int64_t)H * W < (1ll << 31), EVP_ESHAPE,
+                "evp_mvsec_flow_propagate: bad shape (n_frames=%lld %dx%d B=%d max_hops=%d)", (long long)n_frames, H, W, B, max_hops);
+  const dim3 grid((unsigned)ceil_div64((int64_t)H * W, 256), (unsigned)B);
+  if (frames_dtype == EVP_F64)
+    hipLaunchKernelGGL(mvsec_flow_propagate_kernel<double>, grid, dim3(256), 0, (hipStream_t)stream, (const double *)frames, n_frames, H, W,
+                       hop_frame, hop_scale, n_hops, max_hops, label_out, status);
+  else
+    hipLaunchKernelGGL(mvsec_flow_propagate_kernel<float>, grid, dim3(256), 0, (hipStream_t)stream, (const float *)frames, n_frames, H, W,
+                       hop_frame, hop_scale, n_hops, max_hops, label_out, status);
+  EVP_CHECK_LAUNCH("evp_mvsec_flow_propagate");
   return EVP_OK;
 }
 

@@ -9,7 +9,8 @@ dataset.finetune_cls.gpu_event_loader.GpuFinetuneLoader's grid="sensor" recipe i
     the LABEL under the same crop box and flip coins, nearest, back at (H, W)
 
     samples = iterable of (events float64 [n,4] (x,y,t,p) time-sorted numpy array, label, seq_name)
-              task="semseg": label uint8 [H,W];  task="flow": label float32 [2,H,W], what the reader's gen_correspond_gt_flow returns
+              task="semseg": label uint8 [H,W];  task="flow": label float32 [2,H,W], what the reader's gen_correspond_gt_flow returns --
+              or, with gt_flow={seq_name: (flow_dist frames, flow_dist_ts)}, the pair (image1_ts, image2_ts): the label is then made here
     recipe  = dense_recipe(args)                            # args.dataset_type in {"dsec", "ddd17", "mvsec"}
     train   = GpuDenseLoader(args, samples, 64, len(dataset) // 64, True, seed=args.seed, rectify_map=map_or_None, **recipe)
     ft_semseg_train_one_epoch(args, model, train, optimizer, epoch, loss_scaler);  ft_semseg_val(args, model, val, epoch)
@@ -26,7 +27,12 @@ What differs from the classification loader:
   * labels travel with the windows (pinned slot -> one device tensor) and are augmented by evp_semseg_label_augment /
     evp_flow_label_augment_f32 under `chain.crop_rows`, the rows the chain's plan kernel drew for the grids on the device (the reference
     re-seeds numpy with the sample's seed before each of evg_augment, semseg_label_augment, flow_label_augment and
-    flow_label_valid_augment); the flow kernel makes the valid mask (norm > 0 and |flow| < 1000) on the way, so no third plane travels.
+    flow_label_valid_augment); the flow kernel makes the valid mask (norm > 0 and |flow| < 1000) on the way, so no third plane travels;
+  * with `gt_flow` (MVSEC) no flow label travels either: every sequence's ground-truth flow frames are uploaded once at construction, a
+    sample carries its two image timestamps, the pack turns them into a row of hops (mvsec_flow.mvsec_flow_hops, float64 numpy) and
+    evp_mvsec_flow_propagate fills the label buffer from the resident frames in front of the label view -- gen_correspond_gt_flow's
+    propagation (ft_mvsec_dataset.py:121-188), whose cv2.remap nearest rule (half to even) is stated from OpenCV's source, unchecked
+    against a real cv2 (include/evtpretrain.h K29).
 Train: float32 cells. Clean validation: K1 with float64 cells (algo 3) + the bilinear view under the full box, the label kernel under the
 full-box rows (it only widens / makes the mask): a pass repeats bit for bit.
 
@@ -39,11 +45,12 @@ Yields static device tensors the next batch overwrites:
 
 Windows are checked on the host before upload (empty; without a compaction, coordinates outside the sensor; with a map, coordinates
 outside the map: ValueError naming the clip); the device's status words (clips without a survivor, rows outside the map) are read once
-at the end of a pass and raise ValueError when non-zero.
+at the end of a pass and raise ValueError when non-zero. With gt_flow a timestamp outside its sequence's flow frames, an unknown
+sequence name and a sample of more than `max_hops` hops are ValueErrors of the pack.
 
 Out of scope (NotImplementedError): the 2- and 3-bin representations, EvRepSL, and args.val_event_noise -- the reference's dense noisy
 validation clips the added rows to N-Caltech101's cal_sensor_h / cal_sensor_w (ft_dsec_dataset.py:233, ft_mvsec_dataset.py:214), which
-looks like an oversight and is not reproduced. The file readers (h5py, PIL, cv2.remap in gen_correspond_gt_flow) stay with the caller."""
+looks like an oversight and is not reproduced. The file readers (h5py, PIL) stay with the caller."""
 import numpy as np
 import torch
 
@@ -52,6 +59,7 @@ from ..augmentation.view_augment import evg_augment_batch, flow_label_augment_ba
 from ..dataset_utils.events_to_voxel_grid import voxel_grid_batch
 from ..pretrain.gpu_event_loader import ClipWindowLoader
 from ..pretrain.gpu_input_pipeline import GpuInputPipeline
+from .mvsec_flow import MAX_HOPS, mvsec_flow_hops, mvsec_flow_propagate_batch
 
 DDD17_MASK_MARGIN = 10000          # rows of tail the DDD17 recipe uploads beyond the window, for the crop mask to eat into
 MVSEC_MAX_EVENTS = 200_000         # capacity of an MVSEC sample where the namespace has no max_events
@@ -120,16 +128,36 @@ class _CheckedSamples:
             yield events, label, name
 
 
+class _GtFlowSamples:
+    """(events, (image1_ts, image2_ts), seq_name) -> (events, the sample's hop row, seq_name): the schedule is made where the sample is
+    drawn (the pack's worker thread), with the sequence's base index added to its frame indices."""
+
+    def __init__(self, samples, flow_ts, base, max_hops):
+        self.samples, self.flow_ts, self.base, self.max_hops = samples, flow_ts, base, max_hops
+
+    def __iter__(self):
+        for events, stamps, name in self.samples:
+            if name not in self.flow_ts:
+                raise ValueError(f"GpuDenseLoader: sample of sequence {name!r}, gt_flow holds {sorted(self.flow_ts)}")
+            if np.shape(stamps) != (2,):
+                raise ValueError(f"GpuDenseLoader: with gt_flow a sample of {name!r} carries (image1_ts, image2_ts) in the label's place")
+            frames, scales, n_hops = mvsec_flow_hops(self.flow_ts[name], stamps[0], stamps[1], self.max_hops, name=name)
+            frames[:max(n_hops, 1)] += self.base[name]
+            yield events, (frames, scales, n_hops), name
+
+
 class GpuDenseLoader(ClipWindowLoader):
     def __init__(self, args, samples, batch_size, n_batches, is_train, task, sensor, seed=0, first_sample=0, step0=0, rectify_map=None,
-                 org_sensor=None, raw_rows=None, max_events=None, rectify=None, org_view=False):
+                 org_sensor=None, raw_rows=None, max_events=None, rectify=None, org_view=False, gt_flow=None, max_hops=MAX_HOPS):
         """`samples`: a re-iterable (one pass per epoch) of (events, label, seq_name); `n_batches`: batches per pass (a short last batch is
         dropped). `task`: "semseg" | "flow". `sensor`: the (H, W) the grids are binned at and the labels have. `step0`: the counter
         stream's step of the first batch (a training loader continues across epochs, a validation loader restarts there).
         `rectify_map` (float32 [org_h, org_w, 2], numpy or tensor) with `org_sensor` = its (org_h, org_w): DSEC's rectification;
         `raw_rows`: rows of tail uploaded per clip for the crop mask (DDD17); `max_events`: the window's capacity in place of
         args.fix_events_num / val_fix_events_num (MVSEC, which has no fixed count: a longer sample raises ValueError). `rectify`: what
-        dense_recipe says about the map (True needs rectify_map). `org_view`: yield events_voxel_grid_org in training (flow)."""
+        dense_recipe says about the map (True needs rectify_map). `org_view`: yield events_voxel_grid_org in training (flow).
+        `gt_flow` (task="flow"): {seq_name: (frames float32 | float64 [F,2,H,W], flow_ts float64 [F])}, a sequence's flow_dist and
+        flow_dist_ts whole -- uploaded once; a sample is then (events, (image1_ts, image2_ts), seq_name) and may span `max_hops` hops."""
         if task not in ("semseg", "flow"):
             raise ValueError(f"GpuDenseLoader: task must be 'semseg' or 'flow' (got {task!r})")
         if int(args.num_bins) in (2, 3):
@@ -143,6 +171,9 @@ class GpuDenseLoader(ClipWindowLoader):
             raise ValueError("GpuDenseLoader: this recipe rectifies its events (rectify=True): pass the dataset's rectify_map")
         self.task, self.is_train, self.step0, self.org_view = task, bool(is_train), int(step0), bool(org_view)
         H, W = self.sensor = (int(sensor[0]), int(sensor[1]))
+        self._gt_host, self.max_hops = None, int(max_hops)
+        if gt_flow is not None:
+            samples = self._gt_flow_checked(gt_flow, samples)
         fix = int(max_events) if max_events is not None else int(args.fix_events_num if self.is_train else args.val_fix_events_num)
         self.keep = fix
         self.compact = rectify_map is not None or raw_rows is not None
@@ -189,13 +220,60 @@ class GpuDenseLoader(ClipWindowLoader):
     def _window_start(self, n, fix, w0):
         return max(n - fix, 0)            # the tail (ft_dsec_dataset.py:202-209, ft_ddd17_dataset.py:126-127); MVSEC: fix is the capacity
 
+    def _gt_flow_checked(self, gt_flow, samples):
+        """The sequences' frames as one host array (uploaded in _alloc_extra) + the samples wrapped so that a hop row travels."""
+        if self.task != "flow":
+            raise ValueError("GpuDenseLoader: gt_flow (MVSEC's ground-truth flow frames) goes with task='flow'")
+        if not gt_flow:
+            raise ValueError("GpuDenseLoader: gt_flow holds no sequence")
+        if self.max_hops < 2:
+            raise ValueError(f"GpuDenseLoader: max_hops = {self.max_hops} (a propagated label takes at least 2 hops)")
+        parts, flow_ts, base, n = [], {}, {}, 0
+        for name, (frames, ts) in gt_flow.items():
+            f = frames.numpy() if torch.is_tensor(frames) else np.asarray(frames)
+            ts = np.ascontiguousarray(ts.numpy() if torch.is_tensor(ts) else ts)
+            if f.dtype not in (np.float32, np.float64) or f.ndim != 4 or f.shape[1] != 2 or tuple(f.shape[2:]) != self.sensor:
+                raise ValueError(f"GpuDenseLoader: gt_flow[{name!r}] frames must be float32 or float64 [F,2,{self.sensor[0]},{self.sensor[1]}] "
+                                 f"(got {f.dtype} {list(f.shape)})")
+            if parts and f.dtype != parts[0].dtype:
+                raise ValueError(f"GpuDenseLoader: gt_flow[{name!r}] frames are {f.dtype}, the sequences before it {parts[0].dtype}: one dtype for all")
+            if ts.dtype != np.float64 or ts.shape != (f.shape[0],) or f.shape[0] < 2:
+                raise ValueError(f"GpuDenseLoader: gt_flow[{name!r}] flow_ts must be float64 [{f.shape[0]}], one per frame, at least two "
+                                 f"(got {ts.dtype} {list(ts.shape)})")
+            parts.append(f), flow_ts.update({name: ts}), base.update({name: n})
+            n += int(f.shape[0])
+        self._gt_host, self.gt_base = parts, base
+        return _GtFlowSamples(samples, flow_ts, base, self.max_hops)
+
     def _alloc_extra(self):
         H, W = self.sensor
         shape, dtype = ((self.B, 1, H, W), torch.uint8) if self.task == "semseg" else ((self.B, 2, H, W), torch.float32)
         self._lab = torch.zeros(*shape, dtype=dtype, device=self.dev)
+        self.gt_frames = self.gt_status = None
+        if self._gt_host is not None:
+            # every sequence's frames back to back, uploaded once; a batch's hop rows in ONE pinned buffer of int64 words:
+            # [B, max_hops] frame indices | [B, max_hops] float64 scales | B int32 hop counts
+            self.gt_frames = torch.cat([torch.from_numpy(np.ascontiguousarray(f)).to(self.dev) for f in self._gt_host], 0).contiguous()
+            self._gt_host = None
+            B, mh = self.B, self.max_hops
+            self._hops = torch.zeros(2 * B * mh + (B + 1) // 2, dtype=torch.int64, device=self.dev)
+            self._pin_hops = [torch.zeros_like(self._hops, device="cpu").pin_memory() for _ in range(2)]
+            self._hop_frame, self._hop_scale, self._n_hops = self._hop_views(self._hops)
+            self.gt_status = torch.zeros(1, dtype=torch.int32, device=self.dev)
+            return
         self._pin_lab = [torch.zeros(*shape, dtype=dtype).pin_memory() for _ in range(2)]
 
+    def _hop_views(self, words):
+        """One buffer of int64 words (a tensor or a numpy array) -> (frames int64 [B,mh], scales float64 [B,mh], n_hops int32 [B])."""
+        B, mh = self.B, self.max_hops
+        f64, i32 = (torch.float64, torch.int32) if torch.is_tensor(words) else (np.float64, np.int32)
+        return words[:B * mh].reshape(B, mh), words[B * mh:2 * B * mh].view(f64).reshape(B, mh), words[2 * B * mh:].view(i32)[:B]
+
     def _pack_extra(self, slot, i, label):
+        if self.gt_frames is not None:
+            frames, scales, n_hops = self._hop_views(self._pin_hops[slot].numpy())
+            frames[i], scales[i], n_hops[i] = label[0], label[1], label[2]
+            return
         dst = self._pin_lab[slot][i].numpy()
         lab = label.numpy() if torch.is_tensor(label) else np.asarray(label)
         # semseg: uint8 [H,W] (or [1,H,W]); flow: float32 [2,H,W]
@@ -205,6 +283,9 @@ class GpuDenseLoader(ClipWindowLoader):
         dst[...] = lab.reshape(dst.shape)
 
     def _upload_extra(self, slot):
+        if self.gt_frames is not None:
+            self._hops.copy_(self._pin_hops[slot], non_blocking=True)       # a few KB in the label planes' place
+            return
         self._lab.copy_(self._pin_lab[slot], non_blocking=True)
 
     def _check_window(self, window, name):
@@ -223,7 +304,13 @@ class GpuDenseLoader(ClipWindowLoader):
                 raise ValueError(f"GpuDenseLoader: clip {name!r} has an event outside the {H} x {W} sensor")
 
     def _status_checked(self):
-        """End of a pass: the compaction's status words, read once."""
+        """End of a pass: the device's status words, read once."""
+        if self.gt_status is not None:
+            skipped = int(self.gt_status.item())
+            if skipped:
+                self.gt_status.zero_()
+                raise ValueError(f"GpuDenseLoader: evp_mvsec_flow_propagate skipped {skipped} sample(s) of this pass whose hop table names "
+                                 f"no frame of gt_flow ({self.gt_frames.shape[0]} frames, max_hops = {self.max_hops})")
         if self.status is None:
             return
         empty, outside = (int(v) for v in self.status.tolist())
@@ -261,6 +348,9 @@ class GpuDenseLoader(ClipWindowLoader):
                     batch["events_voxel_grid_org"] = self.raw
                 elif self.org_view:
                     batch["events_voxel_grid_org"] = evg_augment_batch(self.raw, rows, (H, W), out=self.org, mode="bilinear")
+                if self.gt_frames is not None:
+                    # the label itself, from the resident frames and the uploaded hop rows, into the buffer the label view reads
+                    mvsec_flow_propagate_batch(self.gt_frames, self._hop_frame, self._hop_scale, self._n_hops, self._lab, self.gt_status)
                 batch["flow_label"], batch["flow_label_valid"] = flow_label_augment_batch(self._lab, rows, (H, W), out=self.label, valid_out=self.valid)
             batch["seq_name"] = names
             yield batch

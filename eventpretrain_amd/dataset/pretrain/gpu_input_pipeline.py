@@ -52,6 +52,7 @@ clip -- a captured chain takes its `fused_voxel=False` form -- and the datasets'
 stage. `rescale=False` counts UNSCALED events on the S x S grid (ES-ImageNet's 2-channel branch), `norm_guard` is the `factor = 1.0 /
 0.001` of the datasets that have it. `image_status` (int32 [2] on the device, accumulated) counts the rows outside the grid and the
 all-zero 3-channel views. grid="window" has no count images (NotImplementedError)."""
+import gc
 from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
@@ -536,8 +537,19 @@ class CapturedChain:
         torch.cuda.current_stream().wait_stream(side)
         torch.cuda.synchronize()
         self.graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(self.graph, stream=side, capture_error_mode="thread_local"):      # (RCCL's watchdog thread may poll its events meanwhile)
-            self.out, self.tgt = self._launches()
+        # torch.cuda.graph no longer collects garbage on entry. A dead reference cycle that owns GPU resources (a loader whose pack raised:
+        # its traceback holds it, with its pinned slots, streams and its own captured graph) must not be collected INSIDE the capture --
+        # releasing them is not a capturable call on the capturing thread, and the process aborts. Collect before, as engine.py's captures
+        # do, and keep the cyclic collector out of the capture itself.
+        gc.collect()
+        collecting = gc.isenabled()
+        gc.disable()
+        try:
+            with torch.cuda.graph(self.graph, stream=side, capture_error_mode="thread_local"):      # (RCCL's watchdog thread may poll its events meanwhile)
+                self.out, self.tgt = self._launches()
+        finally:
+            if collecting:
+                gc.enable()
         if self.self_driven:
             self.set_state(0, 0)                      # the warm-up advanced it
         if self.window:

@@ -13,7 +13,7 @@
  *    capturable in a HIP graph.
  *  - Return value: EVP_OK (0) or a negative evp_status; evp_last_error() gives a thread-local message. Nothing
  *    throws across the ABI.
- *  - dtype codes: EVP_F32 = 0 (float), EVP_BF16 = 1 (bfloat16, raw uint16 storage).
+ *  - dtype codes: EVP_F32 = 0 (float), EVP_BF16 = 1 (bfloat16, raw uint16 storage), EVP_F64 = 2 (double; one entry takes it).
  *  - Row-major everywhere; "ld*" are leading dimensions in ELEMENTS.
  */
 #ifndef EVTPRETRAIN_H
@@ -26,14 +26,14 @@ extern "C" {
 #endif
 
 typedef enum { EVP_OK = 0, EVP_EINVAL = -1, EVP_ESHAPE = -2, EVP_ELAUNCH = -3, EVP_EUNSUPPORTED = -4 } evp_status;
-enum { EVP_F32 = 0, EVP_BF16 = 1 };
+enum { EVP_F32 = 0, EVP_BF16 = 1, EVP_F64 = 2 };      /* EVP_F64 (double): only where an entry says so (evp_mvsec_flow_propagate) */
 enum { EVP_ACT_NONE = 0, EVP_ACT_GELU = 1, EVP_ACT_DGELU = 2, EVP_ACT_RELU = 3, EVP_ACT_DRELU = 4 };
 
 const char *evp_last_error(void);
 /* ABI version of this header; bumped on any signature change (2: evp_dropout_fwd takes a device-side seed; evp_gemm_desc lost its
  * stream-K workspace fields in round 3; 3: evp_events_draw_erase_add; 4: keep flags on the window attention; 5: evp_events_plan_batch; entries ADDED since -- evp_cls_metrics,
  * evp_view_augment_bilinear_f32, evp_voxel_scatter_fused_algo_f32, evp_events_window_geometry, evp_events_build_added_hw_f64, evp_semseg_*, evp_flow_*, evp_semseg_label_augment,
- * evp_flow_label_augment_f32, evp_events_rectify_compact_f64, evp_events_rectify_compact_ws_words -- change no signature and keep 5). A host binding must compare evp_abi_version() with EVP_ABI_VERSION at load time. */
+ * evp_flow_label_augment_f32, evp_events_rectify_compact_f64, evp_events_rectify_compact_ws_words, evp_mvsec_flow_propagate -- change no signature and keep 5). A host binding must compare evp_abi_version() with EVP_ABI_VERSION at load time. */
 #define EVP_ABI_VERSION 5
 int evp_abi_version(void);
 /* Name of the code object's target ("gfx950"). */
@@ -758,6 +758,30 @@ int evp_events_rectify_compact_f64(const double *events_in, int64_t n_rows_in, c
                                    int64_t max_rows_per_clip, const float *map, int map_h, int map_w, int H, int W, int64_t keep_last,
                                    double *events_out, int64_t out_rows, int64_t *offsets_out, int32_t *status, int32_t *workspace,
                                    void *stream);
+/* MVSEC's flow label: FinetuneMVSECSeqDataset.gen_correspond_gt_flow (dataset/finetune_flow/ft_mvsec_dataset.py:121-188) for a batch, from
+ * ground-truth flow frames that stay in device memory. frames: frames_dtype (EVP_F32 | EVP_F64) [n_frames,2,H,W], every sequence's frames
+ * back to back. Sample b is row b of the hop table (device: hop_frame int64 [B,max_hops] ABSOLUTE frame indices, hop_scale float64
+ * [B,max_hops], n_hops int32 [B]), which the host makes from the sample's two image timestamps in float64 (:264-272, :127-169):
+ *   n_hops[b] == 0, the direct branch (start > ts[0] && end <= ts[1]): label = frame hop_frame[b,0] times hop_scale[b,0] = (end - start) /
+ *     (ts[1] - ts[0]), (frame dtype)((double)a * scale), then -- a float64 frame -- rounded once more into the float32 label;
+ *   n_hops[b] == n > 0: per output pixel x = its column, y = its row as float32, x_ok = y_ok = true, and for k = 0 .. n-1 with
+ *     (f, s) = (hop_frame[b,k], hop_scale[b,k]), in this order:
+ *       ix = rint(x), iy = rint(y)                      cv2.remap's INTER_NEAREST cell (cvRound: half to even)
+ *       ax = frames[f,0][iy,ix], ay = frames[f,1][iy,ix]   BOTH at the position before the update; a cell outside the frame, and a NaN
+ *                                                       coordinate, read the border's 0
+ *       x_ok &= ax != 0, y_ok &= ay != 0
+ *       x = (float)((double)x + (double)ax * s), y likewise   product and sum each rounded to double, then once to float: no FMA
+ *     label = (x - column, y - row) in float32, a component 0 where its flag fell.
+ *   The reference's schedule: first hop (0, (ts[1] - start) / (ts[1] - ts[0])), middle hops (i, 1.0), last hop (F-1, (end - ts[F-1]) /
+ *   (ts[F] - ts[F-1])) of the F frames it sliced -- two hops through frame 0 when F == 1.
+ * label_out float32 [B,2,H,W]. status (device int32 [1], accumulated: the caller zeroes it) += 1 per sample whose n_hops is negative or
+ * above max_hops or whose table names a frame outside [0, n_frames): such a sample is skipped, its label_out left as it was, and nothing is
+ * read through its table. One thread per output pixel, no atomic but that count.
+ * Equal to the reference's function bit for bit (tests/golden/mvsec_gt_flow.npz) UNDER ONE ASSUMPTION: the half-to-even rule is OpenCV's as
+ * read from its source; the fixture was made with a stand-in for cv2.remap that states the same rule, not with a real cv2. */
+int evp_mvsec_flow_propagate(const void *frames, int frames_dtype, int64_t n_frames, int H, int W, const int64_t *hop_frame,
+                             const double *hop_scale, const int32_t *n_hops, int B, int max_hops, float *label_out, int32_t *status,
+                             void *stream);
 
 /* ------------------------------------------------------------------------------------------------ K30 event-count images
  * The 2- and 3-channel representations of the classification fine-tuning datasets (dataset/dataset_utils/events_to_image.py as every
